@@ -9,7 +9,11 @@ With N > 1 GPUs (torchrun, one process per GPU) every rank processes its own sha
 with the next step's kernels (distributed.SlabExchange); the timed region ends after the last
 step's gather.
 
-Prints ONE JSON line (rank 0). See DESIGN.md §Measurement for the roofline bytes.
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times --steps steps and prints the
+headline keys (value, ms_per_step, config). --full adds every secondary leg after the timed steps:
+the oracle parity check of the last step, stage times and the roofline, rectification, the side
+configs, the matcher legs, the drop-in latency and the CPU baseline (DESIGN.md §Measurement for the
+roofline bytes). --dump-outputs DIR writes the last timed step's outputs as .npy files.
 """
 from __future__ import annotations
 
@@ -934,6 +938,79 @@ def side_leg(dev, name, W, H, nf, F, steps, warmup, stereo, lap, bf, fx, check_f
     return out, ok
 
 
+def headline(args, world, F, W, H, value, ms_per_step, gather, gloo, fe, odist):
+    """The result line's headline keys: what the timed steps alone determine."""
+    return {
+        "metric": METRIC,
+        "value": round(value, 2),
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic",
+        "config": {
+            "workload": "EuRoC-MH01-like stereo 752x480 (BASELINE config 2): ORBextractor L+R "
+                        "(nFeatures=%d, scale 1.2, 8 levels, FAST 20/7) + ComputeStereoMatches" % args.nfeatures,
+            "frames_per_gpu_per_step": F,
+            "images_per_gpu_per_step": 2 * F,
+            "width": W, "height": H,
+            "allgather": gather,
+            "allgather_backend": (args.dist_backend if gather else None),
+            "allgather_bytes_per_rank_per_step": (odist.slab_bytes(2 * F, fe.cap) if gather else 0),
+            "allgather_overlap": (None if not gather else "synchronous host copies (gloo rehearsal)" if gloo else
+                                  "async, double-buffered: step k's gather runs under step k+1's kernels"),
+            "pipelines": args.pipelines,
+            "parallelism": f"frame-sharded x{world}",
+        },
+    }
+
+
+DUMP_BUDGET_BYTES = 48 << 20   # of the sampled per-frame arrays; the whole dump stays under 64 MB
+DUMP_MAX_FRAMES = 64
+DUMP_SEED = 20240
+
+
+def dump_outputs(fe, out_dir):
+    """--dump-outputs: what a caller of the timed path holds after the last timed step, as float32 /
+    float64 .npy files. counts [2F, 2] (keypoints, monoIndex per image) and nmatch [F] are written
+    whole. The per-keypoint arrays are written for a fixed, seeded sample of frames (sample_frames,
+    ascending; images 2f and 2f + 1 of each): keypoints [2S, cap, 7] (x, y, size, angle, response,
+    octave, class_id), descriptors [2S, cap, 32] (bytes as numbers), uright / depth [S, cap]. Rows
+    past an image's keypoint count are padding the caller never reads; they are written as 0."""
+    fe.torch.cuda.synchronize(fe.device)
+    os.makedirs(out_dir, exist_ok=True)
+    F, cap = fe.F, fe.cap
+    per_frame = 2 * cap * (7 + 32) * 4 + 2 * cap * 4
+    S = max(1, min(F, DUMP_MAX_FRAMES, DUMP_BUDGET_BYTES // per_frame))
+    frames = np.sort(np.random.default_rng(DUMP_SEED).choice(F, S, replace=False))
+    img = np.stack([2 * frames, 2 * frames + 1], 1).reshape(-1)
+    t = fe.torch
+    counts = fe.counts.cpu().numpy()
+    live = np.arange(cap)[None, :] < counts[img, 0][:, None]            # [2S, cap]
+    kps = fe.kps[t.from_numpy(img).to(fe.device)].cpu().numpy()          # [2S, cap, 7] i32 records
+    kp = np.empty(kps.shape, np.float32)
+    kp[..., :5] = np.ascontiguousarray(kps[..., :5]).view(np.float32)   # x, y, size, angle, response
+    kp[..., 5:] = kps[..., 5:]                                           # octave, class_id
+    desc = fe.desc[t.from_numpy(img).to(fe.device)].cpu().numpy().astype(np.float32)
+    kp[~live] = 0
+    desc[~live] = 0
+    out = {"sample_frames": frames.astype(np.float64), "counts": counts.astype(np.float32),
+           "nmatch": fe.nmatch.cpu().numpy().astype(np.float32), "keypoints": kp, "descriptors": desc}
+    fidx = t.from_numpy(frames).to(fe.device)
+    if fe.stereo == "rectified":
+        for name, buf in (("uright", fe.uright), ("depth", fe.depth)):
+            a = buf[fidx].cpu().numpy().astype(np.float32)
+            a[~live[0::2]] = 0
+            out[name] = a
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -1018,7 +1095,15 @@ def main():
                     help="every rank uses cuda:0 (rehearse N ranks on a 1-GPU box with --dist-backend gloo)")
     ap.add_argument("--launch-dry-run", action="store_true",
                     help="only the rank plumbing of --gpus N (gloo, no GPU): rank 0 prints n_gpus")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every secondary leg (oracle parity check, stage times and "
+                         "roofline, rectification, side configs, matcher legs, drop-in latency, CPU baseline); "
+                         "without it the run only sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy, float32 / float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rc = maybe_launch(args.gpus, sys.argv[1:])
     if rc is not None:
@@ -1030,7 +1115,7 @@ def main():
     native = (None, None)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         native = start_native_oracle_build()   # compiles while the GPU legs run
 
     import torch
@@ -1095,6 +1180,17 @@ def main():
     elapsed = float(elapsed.item())
     ms_per_step = 1000.0 * elapsed / args.steps
     value = world * F * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(fe, args.dump_outputs)   # before any later leg runs the front end again
+
+    if not args.full:
+        # the plain run: the headline line alone (every secondary leg is behind --full)
+        if rank == 0:
+            print(json.dumps(headline(args, world, F, W, H, value, ms_per_step, gather, gloo, fe, odist)), flush=True)
+        fe.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- checker: the last timed step's outputs against the CPU oracle (outside the timed region)
     parity = None
@@ -1159,33 +1255,8 @@ def main():
         cache = pmc_cache(n_img, W, H)
         valu = pmc_valu(n_img, W, H)
         copy_peak = copy_peak_gbps(torch, dev)
-        result = {
-            "metric": METRIC,
-            "value": round(value, 2),
-            "unit": "frames/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic",
-            "config": {
-                "workload": "EuRoC-MH01-like stereo 752x480 (BASELINE config 2): ORBextractor L+R "
-                            "(nFeatures=%d, scale 1.2, 8 levels, FAST 20/7) + ComputeStereoMatches" % args.nfeatures,
-                "frames_per_gpu_per_step": F,
-                "images_per_gpu_per_step": 2 * F,
-                "width": W, "height": H,
-                "allgather": gather,
-                "allgather_backend": (args.dist_backend if gather else None),
-                "allgather_bytes_per_rank_per_step": (odist.slab_bytes(2 * F, fe.cap) if gather else 0),
-                "allgather_overlap": (None if not gather else "synchronous host copies (gloo rehearsal)" if gloo else
-                                      "async, double-buffered: step k's gather runs under step k+1's kernels"),
-                "pipelines": args.pipelines,
-                "parallelism": f"frame-sharded x{world}",
-            },
+        result = headline(args, world, F, W, H, value, ms_per_step, gather, gloo, fe, odist)
+        result.update({
             "roofline": {
                 "bound": "hbm",
                 "kernel": pf_kernel,
@@ -1207,7 +1278,7 @@ def main():
             "keypoints_per_image_mean": float(counts[:, 0].mean()),
             "stereo_matches_per_frame_mean": float(nm.mean()),
             "parity": parity,
-        }
+        })
         if valu is not None:
             # VALU issue fraction per kernel (committed rocprofv3 counters of this workload on the
             # isolated-timing build: SQ_INSTS_VALU per step over the kernel's own trace time x the

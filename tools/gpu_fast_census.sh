@@ -6,7 +6,7 @@ set -o pipefail
 cd $GRAFT_REPO_ROOT
 export ORBFE_LIB_PARTIAL=1
 export TMPDIR=/tmp
-PCMD="python bench.py --frames 512 --steps 3 --warmup 1 --stage-steps 1 --no-cpu-baseline --no-parity --matcher-steps 0 --rectify-steps 0 --no-side-configs --dropin-frames 0"
+PCMD="python bench.py --full --frames 512 --steps 3 --warmup 1 --stage-steps 1 --no-cpu-baseline --no-parity --matcher-steps 0 --rectify-steps 0 --no-side-configs --dropin-frames 0"
 for so in variants/liborbfe_fast*.so; do
   n=$(basename $so .so)
   D=gpurun_out/fc_${n}

@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT
 export ORBFE_LIB_PARTIAL=1   # A/B baselines built from older commits may predate entry points
 export TMPDIR=/tmp
 K=${KREGEX:-k_fast}
-PCMD="python bench.py --frames 512 --steps 2 --warmup 1 --stage-steps 1 --no-cpu-baseline --no-parity --matcher-steps 0 --rectify-steps 0 --no-side-configs"
+PCMD="python bench.py --full --frames 512 --steps 2 --warmup 1 --stage-steps 1 --no-cpu-baseline --no-parity --matcher-steps 0 --rectify-steps 0 --no-side-configs"
 for so in variants/liborbfe_*.so; do
   n=$(basename $so .so)
   i=0
