@@ -704,7 +704,10 @@ int orbfe_matcher_last_stats(long long* out);
  * 1 = per-cell FAST key slots (uint32[n_cells * cell_cap], x_rel | y_rel << 12 | score << 24),
  * 2 = DistributeOctTree output (uint32[n], x | y << 12 | score << 24) followed by nothing,
  * 3 = per-level info int32[4] {n, n_lap, n_mono, n_raw},
- * 4 = octree phase timestamps uint64[64] of image 0 (only with ORBFE_OCT_STAMPS set at create).
+ * 4 = octree phase timestamps uint64[64] of image 0 (only with ORBFE_OCT_STAMPS set at create),
+ * 5 = how the last batch built `level`, int32[4] {one-launch pyramid tiles (0: the geometry does not
+ *     fit it), builder (0 the caller's image, 1 one-launch pyramid, 2 row-streamed resize, 3 tiled
+ *     resize), the level fits the row-streamed resize, pitch and every pointer 4-byte aligned}.
  * Returns the element count. */
 int orbfe_debug_copy(orbfe_extractor* h, int what, int image, int level, void* dst, int cap_bytes);
 

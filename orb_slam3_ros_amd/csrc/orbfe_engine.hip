@@ -146,6 +146,8 @@ struct orbfe_extractor {
     std::mutex mu_stereo;
     // last batch description
     int last_nimg = 0, last_pitch = 0;
+    // how the last batch built its pyramid (orbfe_debug_copy what = 5): 1 k_pyramid, 2 k_resize_s, 3 k_resize
+    int last_al0 = 0, last_builder[ORBFE_MAX_LEVELS] = {};
     // extraction counter (every run_batch) and the matcher view of the last orbfe_frame_stereo call:
     // its id, left keypoint count, and the scale factors on the device (orbfe_frame_device_view)
     uint64_t frame_id = 0, fs_id = 0;
@@ -660,6 +662,8 @@ static int run_batch(orbfe_extractor* h, int B, const uint8_t* const* host_ptrs,
         // unless the level's column windows break its rules (then the LDS-tiled k_resize)
         // a small batch: the whole pyramid in one launch (k_pyramid) when the tiles fit its limits
         const bool fused_pyr = h->pt_n > 0 && !h->no_fused_pyramid && (small || h->fused_pyramid_batch);
+        h->last_al0 = al0 ? 1 : 0;
+        for (int l = 1; l < g.nlevels; l++) h->last_builder[l] = fused_pyr ? 1 : (g.lv[l].rs_ok && (l > 1 || al0)) ? 2 : 3;
         if (fused_pyr)
             hipLaunchKernelGGL(k_pyramid, dim3(h->pt_n, B), dim3(PYR_NT), h->pt_lds, s, P, pitch, h->d_pyr, g.pyr_bytes, g,
                                h->d_ptile, h->pt_stride, h->pt_cap, al0 ? 1 : 0);
@@ -1416,6 +1420,12 @@ int orbfe_debug_copy(orbfe_extractor* h, int what, int image, int level, void* d
     else if (what == 1) { src = h->d_cellkeys + (size_t)image * g.cellkeys_per_img + L.cellkey_off; count = ncell * L.cell_cap; bytes = 4 * (size_t)count; }
     else if (what == 2) { src = h->d_outkeys + (size_t)image * g.out_per_img + L.out_off; count = info[0]; bytes = 4 * (size_t)count; }
     else if (what == 3) { if (cap_bytes < 16) return ORBFE_E_CAPACITY; memcpy(dst, info, 16); return 4; }
+    else if (what == 5) {
+        if (cap_bytes < 16) return ORBFE_E_CAPACITY;
+        const int path[4] = {h->pt_n, level ? h->last_builder[level] : 0, L.rs_ok, h->last_al0};
+        memcpy(dst, path, 16);
+        return 4;
+    }
     else if (what == 4) {
         if (!h->d_oct_ts) return 0;
         src = h->d_oct_ts + 64 * level; count = 64; bytes = 64 * 8;
