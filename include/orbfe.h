@@ -327,6 +327,37 @@ int orbfe_search_by_bow(const orbfe_keypoint* kf_keys, const uint8_t* kf_desc, c
                         const orbfe_feature_vector* kf_fv, const orbfe_frame* F, const orbfe_feature_vector* f_fv,
                         int32_t* out, float nnratio, int32_t checkOri);
 
+/* A keyframe kept on the device for the relocalisation candidates loop (Tracking::Relocalization,
+ * Tracking.cc:3680-3701): the parts of a KeyFrame SearchByBoW reads that never change after its
+ * construction (the keypoint angles, mDescriptors, mFeatVec) are copied into HBM once.
+ * orbfe_keyframe_create reads KF->n, keys, desc and device (the other fields are ignored). Keys follow
+ * orbfe_search_by_bow's kf_keys rule: mvKeysUn, or mvKeys ++ mvKeysRight for a two-camera keyframe.
+ * KF->device == 1 (a view of orbfe_frame_device_view) is copied device to device; KF->device == 0 is
+ * host memory; fv is always host memory and is validated as orbfe_search_by_bow validates it
+ * (offsets start at 0 and do not decrease, node ids strictly ascend, every index < n), else
+ * ORBFE_E_ARG. The handle belongs to the HIP device current at create (using it with another device
+ * current returns ORBFE_E_ARG), is immutable and may be used from any thread at once.
+ * orbfe_keyframe_destroy(NULL) is a no-op; destroy must not race a call that uses the handle (the
+ * caller orders them, as it orders KeyFrame deletion). create and destroy may wait for the device. */
+typedef struct orbfe_keyframe orbfe_keyframe;
+int orbfe_keyframe_create(const orbfe_frame* KF, const orbfe_feature_vector* fv, orbfe_keyframe** out);
+void orbfe_keyframe_destroy(orbfe_keyframe* kf);
+int orbfe_keyframe_n(const orbfe_keyframe* kf);
+
+/* SearchByBoW(kfs[c], F, out[c]) for c in [0, n_kfs) in one call and one kernel launch, one workgroup
+ * per candidate. kfs[c] == NULL is a discarded candidate (pKF->isBad()): its row is all -1 and
+ * nmatches[c] = 0. kf_mp[c]: [orbfe_keyframe_n(kfs[c])] map-point handles with bad / NULL points as
+ * -1, host memory, read on every call (the only per-candidate upload). F: a host view or a device
+ * view (orbfe_frame_device_view; its keys / desc are then read in HBM); f_fv: host. out: [n_kfs][F->n];
+ * nmatches: [n_kfs]. Row c is bit-identical to orbfe_search_by_bow on the same inputs (two-camera F
+ * included); a candidate that does not fit one workgroup's LDS takes the multi-launch kernels inside
+ * the same call, still without re-uploading the keyframe. The results are complete on return.
+ * n_kfs == 0 returns ORBFE_OK; n_kfs < 0, a NULL out or a NULL nmatches return ORBFE_E_ARG; both
+ * before any device call. Returns ORBFE_OK or a negative code. */
+int orbfe_search_by_bow_batch(const orbfe_keyframe* const* kfs, const int32_t* const* kf_mp, int32_t n_kfs,
+                              const orbfe_frame* F, const orbfe_feature_vector* f_fv, int32_t* out,
+                              int32_t* nmatches, float nnratio, int32_t checkOri);
+
 /* ComputeStereoFishEyeMatches' descriptor stage (Frame.cc:1126-1151): BFMatcher(NORM_HAMMING)
  * knnMatch(k=2) of left rows [0, nl) against right rows [0, nr) and Lowe's 0.7 ratio. out_train[i]
  * = best right row of left row i or -1; out_dist[i] its distance. The KannalaBrandt8

@@ -119,6 +119,10 @@ _SIGS = {
                                                  _c_float, _vp, _vp]),
     "orbfe_extractor_frame_id": (ctypes.c_uint64, [_vp]),
     "orbfe_frame_device_view": (_c_int, [_vp, ctypes.c_uint64, _vp]),
+    "orbfe_keyframe_create": (_c_int, [_vp, _vp, ctypes.POINTER(_vp)]),
+    "orbfe_keyframe_destroy": (None, [_vp]),
+    "orbfe_keyframe_n": (_c_int, [_vp]),
+    "orbfe_search_by_bow_batch": (_c_int, [_vp, _vp, _c_int, _vp, _vp, _vp, _vp, _c_float, _c_int]),
 }
 
 _lib = None

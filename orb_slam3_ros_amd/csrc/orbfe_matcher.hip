@@ -15,6 +15,7 @@
 #pragma once
 #include "glibc_atan2f.h"
 #include "glibc_logf.h"
+#include <memory>
 
 #define MT_NT 256
 #define MT_TH_HIGH 100
@@ -3116,6 +3117,264 @@ __global__ __launch_bounds__(MT_BOW_NT) void k_bow_block(BowBlockIn in, int* out
 #endif
 }
 
+// SearchByBoW(kfs[c], F) for every candidate of Tracking::Relocalization's first loop in ONE launch
+// (Tracking.cc:3680-3701): workgroup c is k_bow_block on candidate c. The keyframe side is the
+// resident pack of an orbfe_keyframe (node ids, CSR, angles, descriptors: what the search reads, laid
+// out at create so that staging is one flat 16-byte copy); the frame side (node ids, CSR, descriptors,
+// keypoints) is in HBM once for all workgroups; only kf_mp[c] crosses the link per candidate. A KF
+// node finds its F node by binary search of F's node ids in LDS (the reference's lower_bound walk,
+// ORBmatcher.cc:244-371, gives the same pairs), so no pair list exists.
+struct BowCand {
+    const uint4* pack;   // the resident pack: node ids at byte 0, then the arrays at the offsets below
+    int nvec;            // 16-byte words of the pack
+    int o_off, o_idx, o_ang, o_desc;
+    int nn, kf_n;        // nodes, features
+    int mp_vec;          // kf_mp[c]: 16-byte word index from BowBatchIn::mp_base
+    int mode;            // 0: match here; 1: NULL / empty candidate, the row is -1; 2: the multi-launch
+                         //    path (k_bow_nodes + k_bow_commit_ang) writes this row
+};
+struct BowBatchIn {
+    const BowCand* cands;
+    const uint4* fmeta;    // F's node ids at byte 0, offsets at o_foff, indices at o_fidx
+    int nvec_fm, o_foff, o_fidx, fnn;
+    const uint4* fdesc;    // [fn][2]
+    const OrbKeyPoint* fkeys;
+    const uint4* mp_base;
+    int fn, nleft, checkOri;
+    float nnratio;
+    int* out;              // [n_kfs][fn]
+    int* nm;               // [n_kfs]
+};
+// LDS bytes of candidate (nvec, kf_n) against a frame of (nvec_fm, fn): the host's fit test and the
+// kernel's layout (frame meta, F descriptors, pack, kf_mp, F index -> matched KF index)
+__host__ __device__ inline size_t bow_batch_lds(int nvec_fm, int fn, int nvec, int kf_n) {
+    return ((size_t)nvec_fm + 2 * (size_t)fn + (size_t)nvec + (size_t)((kf_n + 3) / 4)) * 16 + (size_t)fn * 4;
+}
+__global__ __launch_bounds__(MT_BOW_NT) void k_bow_batch(BowBatchIn in) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t bb_sm[];
+    __shared__ int s_hist[MT_HISTO];
+    __shared__ unsigned s_keep;
+    __shared__ int s_n;
+    const int tid = threadIdx.x, c = blockIdx.x;
+    // every lane reads the same record: the branches and trip counts below are workgroup-uniform, so
+    // the whole workgroup leaves here or reaches every SYNC()
+    const BowCand cd = in.cands[c];
+    if (cd.mode == 2) return;
+    int* out = in.out + (size_t)c * in.fn;
+    if (cd.mode != 0) {
+        for (int i = tid; i < in.fn; i += MT_BOW_NT) out[i] = -1;
+        if (tid == 0) in.nm[c] = 0;
+        return;
+    }
+    // F's angles for the commit, loaded now (their latency hides under the staging and the walks)
+    float fang[MT_BOW_FR];
+#pragma unroll
+    for (int u = 0; u < MT_BOW_FR; u++) {
+        const int i = tid + u * MT_BOW_NT;
+        fang[u] = i < in.fn ? in.fkeys[i].angle : 0.f;
+    }
+    uint4* s_fm = (uint4*)bb_sm;
+    uint4* s_fdw = s_fm + in.nvec_fm;
+    uint4* s_kf = s_fdw + 2 * in.fn;
+    uint4* s_mpw = s_kf + cd.nvec;
+    int* s_src = (int*)(s_mpw + (cd.kf_n + 3) / 4);   // F index -> matched KF index (-1)
+    const uint4* g_mp = in.mp_base + cd.mp_vec;
+#pragma unroll 4
+    for (int i = tid; i < cd.nvec; i += MT_BOW_NT) s_kf[i] = cd.pack[i];
+#pragma unroll 4
+    for (int i = tid; i < 2 * in.fn; i += MT_BOW_NT) s_fdw[i] = in.fdesc[i];
+    for (int i = tid; i < in.nvec_fm; i += MT_BOW_NT) s_fm[i] = in.fmeta[i];
+    for (int i = tid; i < (cd.kf_n + 3) / 4; i += MT_BOW_NT) s_mpw[i] = g_mp[i];
+    for (int i = tid; i < in.fn; i += MT_BOW_NT) s_src[i] = -1;
+    if (tid < MT_HISTO) s_hist[tid] = 0;
+    if (tid == 0) s_n = 0;
+    SYNC();
+    const unsigned* s_fnid = (const unsigned*)s_fm;
+    const int* s_fo = (const int*)((const uint8_t*)s_fm + in.o_foff);
+    const int* s_fi = (const int*)((const uint8_t*)s_fm + in.o_fidx);
+    const unsigned* s_knid = (const unsigned*)s_kf;
+    const int* s_kfo = (const int*)((const uint8_t*)s_kf + cd.o_off);
+    const int* s_kfi = (const int*)((const uint8_t*)s_kf + cd.o_idx);
+    const float* s_ang = (const float*)((const uint8_t*)s_kf + cd.o_ang);
+    const uint4* s_kd = (const uint4*)((const uint8_t*)s_kf + cd.o_desc);
+    const uint4* s_fd = s_fdw;
+    const int* s_mp = (const int*)s_mpw;
+    // the node walks are k_bow_block's, restated (that kernel stays as it is): one quad of lanes per KF
+    // node, the node's KF features in the reference's order, the quad minimum of (dist, position) keys
+    // the reference's first best
+    const int sl = tid & 3;
+    auto quad_min64 = [](unsigned long long v) {
+        v = mt_min64_dpp_step<0xB1>(v);
+        return mt_min64_dpp_step<0x4E>(v);
+    };
+    constexpr int FQ = 4;   // F features per lane held in registers (nodes of <= 16 F features)
+    for (int a = tid >> 2; a < cd.nn; a += MT_BOW_NT / 4) {
+        const unsigned id = s_knid[a];
+        int b = 0, hi = in.fnn;   // lower_bound of the node id among F's (the quad's lanes agree)
+        while (b < hi) {
+            const int mid = (b + hi) >> 1;
+            if (s_fnid[mid] < id) b = mid + 1;
+            else hi = mid;
+        }
+        if (b >= in.fnn || s_fnid[b] != id) continue;
+        const int fb0 = s_fo[b], fb1 = s_fo[b + 1];
+        const int ka0 = s_kfo[a], ka1 = s_kfo[a + 1];
+        if (fb1 - fb0 <= 4 * FQ) {
+            uint4 fd0[FQ], fd1[FQ];
+            int fidx[FQ];
+            unsigned taken = 0u, isleft = 0u;
+#pragma unroll
+            for (int q = 0; q < FQ; q++) {
+                const int ib = fb0 + sl + 4 * q;
+                fidx[q] = ib < fb1 ? s_fi[ib] : 0;
+                if (ib < fb1) {
+                    fd0[q] = s_fd[2 * fidx[q]];
+                    fd1[q] = s_fd[2 * fidx[q] + 1];
+                    if (in.nleft < 0 || fidx[q] < in.nleft) isleft |= 1u << q;
+                } else {
+                    fd0[q] = fd1[q] = make_uint4(0u, 0u, 0u, 0u);
+                    taken |= 1u << q;
+                }
+            }
+            for (int ia = ka0; ia < ka1; ia++) {
+                const int realIdxKF = s_kfi[ia];
+                if (s_mp[realIdxKF] < 0) continue;
+                const uint4 k0 = s_kd[2 * realIdxKF], k1 = s_kd[2 * realIdxKF + 1];
+                unsigned long long b1 = ~0ull, b2 = ~0ull, r1 = ~0ull;
+#pragma unroll
+                for (int q = 0; q < FQ; q++) {
+                    if ((taken >> q) & 1u) continue;
+                    const int dist = __popc(k0.x ^ fd0[q].x) + __popc(k0.y ^ fd0[q].y) + __popc(k0.z ^ fd0[q].z) +
+                                     __popc(k0.w ^ fd0[q].w) + __popc(k1.x ^ fd1[q].x) + __popc(k1.y ^ fd1[q].y) +
+                                     __popc(k1.z ^ fd1[q].z) + __popc(k1.w ^ fd1[q].w);
+                    const unsigned long long key = ((unsigned long long)dist << 32) | (unsigned)(4 * q + sl);
+                    if ((isleft >> q) & 1u) {
+                        if (key < b1) { b2 = b1; b1 = key; }
+                        else if (key < b2) b2 = key;
+                    } else if (key < r1) {
+                        r1 = key;
+                    }
+                }
+                const unsigned long long m1 = quad_min64(b1);
+                const unsigned long long m2 = quad_min64(b1 == m1 ? b2 : b1);
+                const unsigned long long mr = quad_min64(r1);
+                const int bestDist1 = m1 != ~0ull ? (int)(m1 >> 32) : 256;
+                const int bestDist2 = m2 != ~0ull ? (int)(m2 >> 32) : 256;
+                const int bestDist1R = mr != ~0ull ? (int)(mr >> 32) : 256;
+                int w1 = -1, wr = -1;   // winning positions
+                if (bestDist1 <= MT_TH_LOW) {
+                    if (static_cast<float>(bestDist1) < in.nnratio * static_cast<float>(bestDist2)) w1 = (int)(m1 & 0xFFFFFFFFu);
+                    if (bestDist1R <= MT_TH_LOW) wr = (int)(mr & 0xFFFFFFFFu);
+                }
+#pragma unroll
+                for (int q = 0; q < FQ; q++) {
+                    if (w1 == 4 * q + sl || wr == 4 * q + sl) {
+                        taken |= 1u << q;
+                        s_src[fidx[q]] = realIdxKF;
+                    }
+                }
+            }
+            continue;
+        }
+        // larger nodes: the F features and their flags read from LDS per KF feature
+        for (int ia = ka0; ia < ka1; ia++) {
+            const int realIdxKF = s_kfi[ia];
+            if (s_mp[realIdxKF] < 0) continue;
+            const uint4 k0 = s_kd[2 * realIdxKF], k1 = s_kd[2 * realIdxKF + 1];
+            unsigned long long b1 = ~0ull, b2 = ~0ull, r1 = ~0ull;
+            for (int ib = fb0 + sl; ib < fb1; ib += 4) {
+                const int realIdxF = s_fi[ib];
+                if (s_src[realIdxF] >= 0) continue;
+                const uint4 f0 = s_fd[2 * realIdxF], f1 = s_fd[2 * realIdxF + 1];
+                const int dist = __popc(k0.x ^ f0.x) + __popc(k0.y ^ f0.y) + __popc(k0.z ^ f0.z) + __popc(k0.w ^ f0.w) +
+                                 __popc(k1.x ^ f1.x) + __popc(k1.y ^ f1.y) + __popc(k1.z ^ f1.z) + __popc(k1.w ^ f1.w);
+                const unsigned long long key = ((unsigned long long)dist << 32) | (unsigned)ib;
+                if (in.nleft < 0 || realIdxF < in.nleft) {
+                    if (key < b1) { b2 = b1; b1 = key; }
+                    else if (key < b2) b2 = key;
+                } else if (key < r1) {
+                    r1 = key;
+                }
+            }
+            const unsigned long long m1 = quad_min64(b1);
+            const unsigned long long m2 = quad_min64(b1 == m1 ? b2 : b1);
+            const unsigned long long mr = quad_min64(r1);
+            if (sl == 0) {
+                const int bestDist1 = m1 != ~0ull ? (int)(m1 >> 32) : 256;
+                const int bestDist2 = m2 != ~0ull ? (int)(m2 >> 32) : 256;
+                const int bestDist1R = mr != ~0ull ? (int)(mr >> 32) : 256;
+                if (bestDist1 <= MT_TH_LOW) {
+                    if (static_cast<float>(bestDist1) < in.nnratio * static_cast<float>(bestDist2))
+                        s_src[s_fi[(int)(m1 & 0xFFFFFFFFu)]] = realIdxKF;
+                    if (bestDist1R <= MT_TH_LOW) s_src[s_fi[(int)(mr & 0xFFFFFFFFu)]] = realIdxKF;
+                }
+            }
+            WAVE_SYNC();   // the quad's next KF feature sees the taken F features
+        }
+    }
+    SYNC();
+    // rotation consistency (ORBmatcher.cc:373-395) and the output row
+    int sidx[MT_BOW_FR], bin[MT_BOW_FR];
+#pragma unroll
+    for (int u = 0; u < MT_BOW_FR; u++) {
+        const int i = tid + u * MT_BOW_NT;
+        sidx[u] = i < in.fn ? s_src[i] : -1;
+        bin[u] = sidx[u] >= 0 ? mt_rot_bin(s_ang[sidx[u]], fang[u]) : 0;
+        if (sidx[u] >= 0 && in.checkOri) atomicAdd(&s_hist[bin[u]], 1);
+    }
+    SYNC();
+    if (tid == 0) s_keep = in.checkOri ? mt_three_maxima_keep(s_hist) : 0xFFFFFFFFu;
+    SYNC();
+    int cnt = 0;
+#pragma unroll
+    for (int u = 0; u < MT_BOW_FR; u++) {
+        const int i = tid + u * MT_BOW_NT;
+        if (i >= in.fn) continue;
+        int o = -1;
+        if (sidx[u] >= 0 && (!in.checkOri || ((s_keep >> bin[u]) & 1u))) o = s_mp[sidx[u]];
+        out[i] = o;
+        cnt += o >= 0 ? 1 : 0;
+    }
+    atomicAdd(&s_n, cnt);
+    SYNC();
+    if (tid == 0) in.nm[c] = s_n;   // the host reads the rows after a stream synchronisation
+}
+// k_bow_commit for a resident keyframe (the pack keeps the angles only): the multi-launch path of a
+// batch candidate that does not fit one workgroup's LDS
+__global__ __launch_bounds__(1024) void k_bow_commit_ang(const float* kf_ang, const OrbKeyPoint* f_keys, int fn,
+                                                         const int32_t* kf_mp, int checkOri, const int* out_src,
+                                                         int* out, int* result) {
+    __shared__ int s_hist[MT_HISTO];
+    __shared__ unsigned s_keep;
+    __shared__ int s_n;
+    if (threadIdx.x < MT_HISTO) s_hist[threadIdx.x] = 0;
+    if (threadIdx.x == 0) s_n = 0;
+    SYNC();
+    for (int i = threadIdx.x; i < fn; i += blockDim.x) {
+        const int s = out_src[i];
+        if (s >= 0 && checkOri) atomicAdd(&s_hist[mt_rot_bin(kf_ang[s], f_keys[i].angle)], 1);
+    }
+    SYNC();
+    if (threadIdx.x == 0) s_keep = checkOri ? mt_three_maxima_keep(s_hist) : 0xFFFFFFFFu;
+    SYNC();
+    int cnt = 0;
+    for (int i = threadIdx.x; i < fn; i += blockDim.x) {
+        const int s = out_src[i];
+        int o = -1;
+        if (s >= 0 && (!checkOri || ((s_keep >> mt_rot_bin(kf_ang[s], f_keys[i].angle)) & 1u))) o = kf_mp[s];
+        out[i] = o;
+        cnt += o >= 0 ? 1 : 0;
+    }
+    atomicAdd(&s_n, cnt);
+    SYNC();
+    if (threadIdx.x == 0) result[0] = s_n;
+}
+// the angles of a device-resident keyframe's keypoints, gathered into its pack at create
+__global__ void k_kf_angles(const OrbKeyPoint* keys, int n, float* ang) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) ang[i] = keys[i].angle;
+}
+
 // ---- ComputeStereoFishEyeMatches' knnMatch(k=2) + ratio (Frame.cc:1144-1151) ----
 __global__ __launch_bounds__(MT_NT) void k_knn2(const uint32_t* L, int nl, const uint32_t* R, int nr, float ratio,
                                                 int* out_train, int* out_dist) {
@@ -4252,6 +4511,19 @@ int sbp_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs
 
 }  // namespace
 
+// A keyframe's matcher-visible immutable features in HBM (orbfe_keyframe_create): one allocation,
+// [node ids | CSR offsets | CSR indices | angles | descriptors], every array at a 16-byte offset, so
+// k_bow_batch stages it with one flat copy. The node ids stay on the host too: the multi-launch path
+// joins them with F's.
+struct orbfe_keyframe {
+    int device = -1;
+    int n = 0, nn = 0;
+    uint8_t* pack = nullptr;
+    int nvec = 0;
+    int o_off = 0, o_idx = 0, o_ang = 0, o_desc = 0;
+    std::vector<uint32_t> node_ids;
+};
+
 extern "C" {
 
 int orbfe_search_by_projection_local(const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs,
@@ -4562,6 +4834,212 @@ int orbfe_search_by_bow(const orbfe_keypoint* kf_keys, const uint8_t* kf_desc, c
     HIPCHK(hipStreamSynchronize(s));
     nm = t_ms.hs[0];
     return nm;
+}
+
+int orbfe_keyframe_create(const orbfe_frame* KF, const orbfe_feature_vector* fv, orbfe_keyframe** out) {
+    if (!out) return ORBFE_E_ARG;
+    *out = nullptr;
+    if (!KF || !fv || KF->n < 0 || fv->n_nodes < 0 || (KF->n > 0 && (!KF->keys || !KF->desc))) return ORBFE_E_ARG;
+    const int n = KF->n, nn = fv->n_nodes;
+    if (nn > 0) {   // orbfe_search_by_bow's checks of a FeatureVector
+        if (!fv->node_ids || !fv->offsets || fv->offsets[0] != 0) return ORBFE_E_ARG;
+        for (int i = 0; i < nn; i++)
+            if (fv->offsets[i + 1] < fv->offsets[i] || (i > 0 && fv->node_ids[i] <= fv->node_ids[i - 1]))
+                return ORBFE_E_ARG;
+    }
+    const int nki = nn > 0 ? fv->offsets[nn] : 0;
+    if (nki > 0 && !fv->indices) return ORBFE_E_ARG;
+    for (int i = 0; i < nki; i++)
+        if (fv->indices[i] >= (uint32_t)n) return ORBFE_E_ARG;
+    auto a16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t o_off = a16((size_t)nn * 4), o_idx = o_off + a16((size_t)(nn + 1) * 4);
+    const size_t o_ang = o_idx + a16((size_t)nki * 4), o_desc = o_ang + a16((size_t)n * 4);
+    const size_t total = o_desc + (size_t)n * 32;
+    if (total > ((size_t)1 << 30)) return ORBFE_E_CAPACITY;
+    std::unique_ptr<orbfe_keyframe> kf(new orbfe_keyframe);
+    HIPCHK(hipGetDevice(&kf->device));
+    kf->n = n;
+    kf->nn = nn;
+    if (nn > 0) kf->node_ids.assign(fv->node_ids, fv->node_ids + nn);
+    if (n == 0 || nki == 0) {   // nothing to match: no pack, every search gives the empty row
+        *out = kf.release();
+        return ORBFE_OK;
+    }
+    kf->nvec = (int)(total / 16);
+    kf->o_off = (int)o_off;
+    kf->o_idx = (int)o_idx;
+    kf->o_ang = (int)o_ang;
+    kf->o_desc = (int)o_desc;
+    std::vector<uint8_t> h(o_desc, 0);
+    memcpy(h.data(), fv->node_ids, (size_t)nn * 4);
+    memcpy(h.data() + o_off, fv->offsets, (size_t)(nn + 1) * 4);
+    memcpy(h.data() + o_idx, fv->indices, (size_t)nki * 4);
+    if (!KF->device) {
+        float* ang = (float*)(h.data() + o_ang);
+        for (int i = 0; i < n; i++) ang[i] = KF->keys[i].angle;
+    }
+    uint8_t* pack = nullptr;
+    HIPCHK(hipMalloc((void**)&pack, total));
+    // the copies below may fail: the pack is released with the handle
+    struct Guard {
+        uint8_t* p;
+        ~Guard() { if (p) (void)hipFree(p); }
+    } guard{pack};
+    HIPCHK(hipMemcpy(pack, h.data(), o_desc, hipMemcpyHostToDevice));
+    if (KF->device) {   // a view of orbfe_frame_device_view: device to device, no host round trip
+        hipLaunchKernelGGL(k_kf_angles, dim3((n + 255) / 256), dim3(256), 0, nullptr, (const OrbKeyPoint*)KF->keys, n,
+                           (float*)(pack + o_ang));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(pack + o_desc, KF->desc, (size_t)n * 32, hipMemcpyDeviceToDevice, nullptr));
+        HIPCHK(hipStreamSynchronize(nullptr));
+    } else {
+        HIPCHK(hipMemcpy(pack + o_desc, KF->desc, (size_t)n * 32, hipMemcpyHostToDevice));
+    }
+    guard.p = nullptr;
+    kf->pack = pack;
+    *out = kf.release();
+    return ORBFE_OK;
+}
+
+void orbfe_keyframe_destroy(orbfe_keyframe* kf) {
+    if (!kf) return;
+    if (kf->pack) (void)hipFree(kf->pack);
+    delete kf;
+}
+
+int orbfe_keyframe_n(const orbfe_keyframe* kf) { return kf ? kf->n : ORBFE_E_ARG; }
+
+int orbfe_search_by_bow_batch(const orbfe_keyframe* const* kfs, const int32_t* const* kf_mp, int32_t n_kfs,
+                              const orbfe_frame* F, const orbfe_feature_vector* f_fv, int32_t* out, int32_t* nmatches,
+                              float nnratio, int32_t checkOri) {
+    if (n_kfs < 0 || !out || !nmatches) return ORBFE_E_ARG;
+    if (n_kfs == 0) return ORBFE_OK;
+    if (!kfs || !kf_mp || !F || F->n < 0 || !f_fv || f_fv->n_nodes < 0) return ORBFE_E_ARG;
+    if (F->two_cams && (F->nleft < 0 || F->nleft > F->n)) return ORBFE_E_ARG;
+    const int fn = F->n, fnn = f_fv->n_nodes;
+    if (fn > 0 && (!F->keys || !F->desc)) return ORBFE_E_ARG;
+    bool any = false;
+    for (int c = 0; c < n_kfs; c++) {
+        nmatches[c] = 0;
+        if (kfs[c] && kfs[c]->n > 0 && !kf_mp[c]) return ORBFE_E_ARG;
+        any = any || (kfs[c] && kfs[c]->pack);
+    }
+    for (size_t i = 0; i < (size_t)n_kfs * fn; i++) out[i] = -1;
+    if (fn == 0 || fnn == 0 || !any) return ORBFE_OK;
+    if (!f_fv->node_ids || !f_fv->offsets || f_fv->offsets[0] != 0) return ORBFE_E_ARG;
+    for (int i = 0; i < fnn; i++)
+        if (f_fv->offsets[i + 1] < f_fv->offsets[i] || (i > 0 && f_fv->node_ids[i] <= f_fv->node_ids[i - 1]))
+            return ORBFE_E_ARG;
+    // each frame index must belong to one node only (DBoW2 transform); the per-node quads rely on it
+    const int nfi = f_fv->offsets[fnn];
+    if (nfi > 0 && !f_fv->indices) return ORBFE_E_ARG;
+    std::vector<uint8_t> seen(fn, 0);
+    for (int i = 0; i < nfi; i++) {
+        const uint32_t x = f_fv->indices[i];
+        if (x >= (uint32_t)fn || seen[x]) return ORBFE_E_ARG;
+        seen[x] = 1;
+    }
+    if (nfi == 0) return ORBFE_OK;
+    if ((size_t)n_kfs * fn + (size_t)n_kfs > ((size_t)1 << 28)) return ORBFE_E_CAPACITY;
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    for (int c = 0; c < n_kfs; c++)
+        if (kfs[c] && kfs[c]->device != dev) return ORBFE_E_ARG;   // a handle belongs to its create's device
+    if (F->device && (((uintptr_t)F->desc) & 15)) return ORBFE_E_ARG;   // staged with 16-byte loads
+    // the frame side, uploaded once for all candidates: node ids, CSR (one contiguous range, staged
+    // whole), then the descriptors and keypoints unless F is a device view
+    Plan p;
+    const size_t o_fnid = p.upload(f_fv->node_ids, (size_t)fnn * 4);
+    const size_t o_foff = p.upload(f_fv->offsets, (size_t)(fnn + 1) * 4);
+    const size_t o_fidx = p.upload(f_fv->indices, (size_t)nfi * 4);
+    const size_t fm_bytes = o_fidx + (size_t)nfi * 4 - o_fnid;
+    const int nvec_fm = (int)((fm_bytes + 15) / 16);
+    const size_t o_fdesc = F->device ? 0 : p.upload(F->desc, (size_t)fn * 32);
+    const size_t o_fkeys = F->device ? 0 : p.upload(F->keys, (size_t)fn * sizeof(orbfe_keypoint));
+    // per candidate: kf_mp, and for one that does not fit a workgroup's LDS (the bounds of
+    // orbfe_search_by_bow's one-workgroup form) the node pairs of the multi-launch path
+    std::vector<BowCand> cands(n_kfs);
+    std::vector<size_t> o_mp(n_kfs, 0), o_pairs(n_kfs, 0), o_src(n_kfs, 0);
+    std::vector<std::vector<int32_t>> pairs(n_kfs);
+    const size_t lds_max = 150 * 1024;
+    size_t lds = 0;
+    int nlive = 0;
+    for (int c = 0; c < n_kfs; c++) {
+        const orbfe_keyframe* k = kfs[c];
+        BowCand& cd = cands[c];
+        memset(&cd, 0, sizeof(cd));
+        cd.mode = 1;
+        if (!k || !k->pack) continue;
+        o_mp[c] = p.upload(kf_mp[c], (size_t)k->n * 4);
+        cd = BowCand{(const uint4*)k->pack, k->nvec, k->o_off, k->o_idx, k->o_ang, k->o_desc, k->nn, k->n, 0, 0};
+        const size_t need = bow_batch_lds(nvec_fm, fn, k->nvec, k->n) + 16;
+        if (need <= lds_max && fn <= MT_BOW_FR * MT_BOW_NT) {
+            lds = std::max(lds, need);
+            nlive++;
+            continue;
+        }
+        // ordered merge-join of the two node lists, as orbfe_search_by_bow
+        int a = 0, b = 0;
+        while (a < k->nn && b < fnn) {
+            if (k->node_ids[a] == f_fv->node_ids[b]) { pairs[c].push_back(a); pairs[c].push_back(b); a++; b++; }
+            else if (k->node_ids[a] < f_fv->node_ids[b]) a++;
+            else b++;
+        }
+        cd.mode = pairs[c].empty() ? 1 : 2;
+        if (cd.mode == 2) o_pairs[c] = p.upload(pairs[c].data(), pairs[c].size() * 4);
+    }
+    for (int c = 0; c < n_kfs; c++) cands[c].mp_vec = (int)((o_mp[c] - o_fnid) / 16);
+    const size_t o_cands = p.upload(cands.data(), (size_t)n_kfs * sizeof(BowCand));
+    for (int c = 0; c < n_kfs; c++)
+        if (cands[c].mode == 2) o_src[c] = p.scratch((size_t)fn * 4);
+    int rc = ms_prepare(p);
+    if (rc) return rc;
+    MatchScratch& m = t_ms;
+    const size_t nout = (size_t)n_kfs * fn + (size_t)n_kfs;   // the rows, then nmatches
+    if (m.ocap < nout) {
+        if (m.ho) HIPCHK(hipHostFree(m.ho));
+        m.ho = nullptr;
+        m.ocap = 0;
+        const size_t cap = std::max<size_t>(nout + nout / 2, 2048);
+        HIPCHK(hipHostMalloc((void**)&m.ho, cap * 4, hipHostMallocMapped | hipHostMallocCoherent));
+        HIPCHK(hipHostGetDevicePointer((void**)&m.ho_dev, m.ho, 0));
+        m.ocap = cap;
+    }
+    MsTimer timer;
+    hipStream_t s = m.stream;
+    int* d_out = m.ho_dev;
+    int* d_nm = m.ho_dev + (size_t)n_kfs * fn;
+    const uint32_t* d_fdesc = F->device ? (const uint32_t*)F->desc : ms_ptr<const uint32_t>(o_fdesc);
+    const OrbKeyPoint* d_fkeys = F->device ? (const OrbKeyPoint*)F->keys : ms_ptr<const OrbKeyPoint>(o_fkeys);
+    const int nleft = F->two_cams ? F->nleft : -1;
+    for (int c = 0; c < n_kfs; c++) {
+        if (cands[c].mode != 2) continue;
+        const orbfe_keyframe* k = kfs[c];
+        const int npairs = (int)pairs[c].size() / 2;
+        fill(ms_ptr<int>(o_src[c]), fn, -1);
+        hipLaunchKernelGGL(k_bow_nodes, dim3((npairs + MT_NT - 1) / MT_NT), dim3(MT_NT), 0, s,
+                           ms_ptr<const int>(o_pairs[c]), npairs, (const int*)(k->pack + k->o_off),
+                           (const uint32_t*)(k->pack + k->o_idx), ms_ptr<const int>(o_foff),
+                           ms_ptr<const uint32_t>(o_fidx), ms_ptr<const int32_t>(o_mp[c]),
+                           (const uint32_t*)(k->pack + k->o_desc), d_fdesc, nnratio, nleft, ms_ptr<int>(o_src[c]));
+        hipLaunchKernelGGL(k_bow_commit_ang, dim3(1), dim3(1024), 0, s, (const float*)(k->pack + k->o_ang), d_fkeys, fn,
+                           ms_ptr<const int32_t>(o_mp[c]), checkOri, ms_ptr<const int>(o_src[c]),
+                           d_out + (size_t)c * fn, d_nm + c);
+    }
+    // one workgroup per candidate; the dynamic LDS is the largest fitting candidate's. A batch whose
+    // candidates all took the multi-launch path still runs it for the empty rows (no LDS then).
+    const BowBatchIn in{ms_ptr<const BowCand>(o_cands), ms_ptr<const uint4>(o_fnid), nvec_fm, (int)(o_foff - o_fnid),
+                        (int)(o_fidx - o_fnid), fnn, (const uint4*)d_fdesc, d_fkeys, ms_ptr<const uint4>(o_fnid), fn,
+                        nleft, checkOri, nnratio, d_out, d_nm};
+    hipLaunchKernelGGL(k_bow_batch, dim3(n_kfs), dim3(MT_BOW_NT), nlive ? lds : 0, s, in);
+    HIPCHK(hipGetLastError());
+    timer.end();
+    // completion: every workgroup's stores (and the multi-launch kernels') are visible in the mapped
+    // pinned block once the stream has drained
+    HIPCHK(hipStreamSynchronize(s));
+    memcpy(out, m.ho, (size_t)n_kfs * fn * 4);
+    memcpy(nmatches, m.ho + (size_t)n_kfs * fn, (size_t)n_kfs * 4);
+    return ORBFE_OK;
 }
 
 int orbfe_stereo_knn_ratio(const uint8_t* left_desc, int32_t nl, const uint8_t* right_desc, int32_t nr, float ratio,

@@ -273,6 +273,28 @@ class FeatureVector:
         return ctypes.byref(self.c)
 
 
+class KeyFrameFeatures:
+    """A keyframe's immutable matcher inputs (keypoint angles, mDescriptors, mFeatVec) kept in HBM
+    (orbfe_keyframe): the candidates of ORBmatcher.SearchByBoWBatch. frame: a MatchFrame (keys follow
+    SearchByBoW's kf_keys rule) or a device view (current_frame_view), which is copied device to
+    device. The arrays may be released after construction; close() (or the finaliser) frees the HBM
+    copy and must not run while a search uses the object."""
+
+    def __init__(self, frame, featvec: FeatureVector):
+        import weakref
+        lib = _lib.load()
+        h = ctypes.c_void_p()
+        _lib.check(lib.orbfe_keyframe_create(frame.ref(), featvec.ref(), ctypes.byref(h)), "KeyFrameFeatures")
+        self.handle = h.value
+        self.N = int(lib.orbfe_keyframe_n(self.handle))
+        self._fin = weakref.finalize(self, lib.orbfe_keyframe_destroy, self.handle)
+
+    def close(self):
+        if self.handle is not None:
+            self._fin()
+            self.handle = None
+
+
 def _i32(a, n, what):
     a = np.asarray(a)
     if a.dtype != np.int32 or not a.flags.c_contiguous or a.size != n:
@@ -390,6 +412,36 @@ class ORBmatcher:
             kk.ctypes.data, kd.ctypes.data, km.ctypes.data, len(kk), kf_featvec.ref(), F.ref(), f_featvec.ref(),
             out.ctypes.data, self.mfNNratio, int(self.mbCheckOrientation)), "SearchByBoW")
         return n, out
+
+    # the candidates loop of Tracking::Relocalization (Tracking.cc:3680-3701): SearchByBoW(vpCandidateKFs[i],
+    # mCurrentFrame, vvpMapPointMatches[i]) for every i in one call
+    def SearchByBoWBatch(self, kfs, kf_map_points, F: MatchFrame, f_featvec: FeatureVector):
+        """kfs: KeyFrameFeatures or None (a discarded candidate, pKF->isBad()) per candidate;
+        kf_map_points[c]: int32 [kfs[c].N] GetMapPointMatches() handles with bad points as -1 (ignored for
+        None). F may be a device view (current_frame_view). Returns (nmatches int32 [C], vvpMapPointMatches
+        int32 [C, F.N]); row c equals SearchByBoW on candidate c."""
+        C = len(kfs)
+        if len(kf_map_points) != C:
+            raise ValueError("one kf_map_points entry per candidate")
+        handles = (ctypes.c_void_p * max(C, 1))()
+        mps = (ctypes.c_void_p * max(C, 1))()
+        keep = []
+        for c, kf in enumerate(kfs):
+            if kf is None:
+                continue
+            if kf.handle is None:
+                raise ValueError("KeyFrameFeatures is closed")
+            km = _i32(np.ascontiguousarray(kf_map_points[c], np.int32), kf.N, "kf_map_points")
+            keep.append(km)
+            handles[c] = kf.handle
+            mps[c] = km.ctypes.data if kf.N else None
+        out = np.full((C, F.N), -1, np.int32)
+        nm = np.zeros(C, np.int32)
+        if C:
+            _lib.check(self._lib.orbfe_search_by_bow_batch(
+                handles, mps, C, F.ref(), f_featvec.ref(), out.ctypes.data, nm.ctypes.data, self.mfNNratio,
+                int(self.mbCheckOrientation)), "SearchByBoW(batch)")
+        return nm, out
 
     # SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12) (:765-903)
     def SearchByBoWKF(self, keys1, desc1, map_points1, featvec1: FeatureVector, keys2, desc2, map_points2,
