@@ -173,6 +173,65 @@ int orbfe_frame_fisheye(orbfe_extractor* left, orbfe_extractor* right, const uin
                         int* mono_right, int32_t* l2r, int32_t* dist);
 
 /* ---------------------------------------------------------------------------------------------
+ * RGB-D — replaces the RGB-D Frame constructor's feature part (src/Frame.cc:200-286:
+ * ExtractORB(0, imGray, 0, 0) :223, UndistortKeyPoints :234 / :747-780, ComputeStereoFromRGBD :236 /
+ * :984-1005) and the depth conversion of Tracking::GrabImageRGBD (Tracking.cc:1576-1577)
+ * ------------------------------------------------------------------------------------------- */
+
+/* What the RGB-D frame reads of the camera: K (mK), DistCoef (mDistCoef: k1 k2 p1 p2 [k3 [k4 k5 k6
+ * [s1..s4]]]), mbf, and mDepthMapFactor as Tracking holds it, already inverted (Tracking.cc:613-617:
+ * 1 / DepthMapFactor, e.g. 1 / 5000 for the TUM sequences). */
+typedef struct orbfe_rgbd_params {
+    float fx, fy, cx, cy;
+    float dist[12];
+    int32_t ndist;        /* 0, 4, 5, 8 or 12; 0 means no distortion */
+    float bf;
+    float depth_factor;
+} orbfe_rgbd_params;
+
+#define ORBFE_DEPTH_U16 0   /* CV_16UC1 depth (TUM, RealSense) */
+#define ORBFE_DEPTH_F32 1   /* CV_32FC1 depth */
+
+/* For every keypoint i of a frame (kp = mvKeys[i], kpU = mvKeysUn[i]):
+ *   mvKeysUn[i] = kp with pt = cv::undistortPoints(pt, K, DistCoef, noArray(), K) (the arithmetic of
+ *     orbfe_undistort_points); when dist[0] == 0 or ndist == 0 the keypoint is copied unchanged,
+ *     whatever the other coefficients are (Frame.cc:749-753);
+ *   d = depth[(int)kp.pt.y][(int)kp.pt.x], the DISTORTED keypoint truncated (Frame.cc:994-998),
+ *     converted as GrabImageRGBD converts the whole image: ORBFE_DEPTH_U16 d = (float)raw *
+ *     depth_factor; ORBFE_DEPTH_F32 d = raw * depth_factor when fabsf(depth_factor - 1) > 1e-5, else
+ *     raw untouched. So the caller passes the RAW depth image and drops its convertTo (a caller that
+ *     keeps it passes ORBFE_DEPTH_F32 with depth_factor 1);
+ *   d > 0: mvDepth[i] = d, mvuRight[i] = kpU.pt.x - bf / d; otherwise (0, negative, NaN) both -1.
+ *
+ * Batched, device-resident, mirroring orbfe_stereo_match_batch: frame f uses image (base + f*step)
+ * of h's last batch and the depth image d_depth[f] (nframes device pointers in a host array; each
+ * image the batch's width x height, row pitch depth_pitch_bytes). Device outputs [nframes][cap]
+ * (cap = orbfe_extractor_capacity): d_keys_un (may be NULL), d_uright, d_depth_out; slots at or past
+ * an image's count are not written. One launch on `stream`, ordered after the batch when that ran on
+ * the same stream; no host synchronisation unless the pointer table changed since the last call.
+ * Before any device call: ORBFE_E_ARG for a NULL h or p, a bad depth_type or ndist, nframes < 0, and
+ * (nframes > 0) a NULL d_depth / d_uright / d_depth_out; nframes == 0 returns ORBFE_OK. A pitch
+ * smaller than one row, a NULL d_depth[f] or images outside the last batch return ORBFE_E_ARG. */
+int orbfe_rgbd_stereo_batch(orbfe_extractor* h, int base, int step, int nframes, const void* const* d_depth,
+                            int depth_type, int depth_pitch_bytes, const orbfe_rgbd_params* p,
+                            orbfe_keypoint* d_keys_un, float* d_uright, float* d_depth_out, void* stream);
+
+/* Frame::Frame(imGray, imDepth, ...) (Frame.cc:222-237) in one call, host images in and host results
+ * out: orbfe_extract(h, img, ..., lap 0, 0, ...) plus kps_un = mvKeysUn, uright = mvuRight,
+ * depth_out = mvDepth ([*n] each; any output pointer but n may be NULL). depth: the raw depth image
+ * at the gray image's width x height, row stride depth_stride_bytes. Returns what orbfe_extract
+ * returns (monoIndex, ORBFE_E_EMPTY for an empty image, *n > cap: ORBFE_E_CAPACITY). One stream
+ * synchronisation: the gray image goes up and the extraction is enqueued, the depth image is copied
+ * into pinned memory while the GPU extracts and goes up by a DMA copy on a second stream beside the
+ * extraction kernels, and the RGB-D kernel waits for that copy. ORBFE_E_ARG before any device call: NULL h /
+ * p / n, a bad depth_type or ndist, stride < width, a NULL depth, a depth stride smaller than one row.
+ * orbfe_get_call_timing(h) then holds {upload, extraction kernels, result copies, the RGB-D kernel
+ * (with any wait for the host's depth copy), 0}. */
+int orbfe_frame_rgbd(orbfe_extractor* h, const uint8_t* img, int width, int height, int stride, const void* depth,
+                     int depth_type, int depth_stride_bytes, const orbfe_rgbd_params* p, orbfe_keypoint* kps,
+                     orbfe_keypoint* kps_un, uint8_t* desc, int cap, int* n, float* uright, float* depth_out);
+
+/* ---------------------------------------------------------------------------------------------
  * ORBmatcher — replaces the Tracking-thread methods of ORB_SLAM3::ORBmatcher (include/ORBmatcher.h)
  * and Frame::ComputeStereoFishEyeMatches' brute-force kNN. Stateless and re-entrant; every call
  * takes host pointers, runs on the current HIP device, and returns nmatches (>= 0) or an error.
@@ -221,7 +280,9 @@ typedef struct orbfe_frame {
  * single-camera searches (orbfe_search_by_projection_local / _lastframe / _kf,
  * orbfe_search_local_points(_track)) take such a view for frames of <= 2048 keypoints and <= 2048
  * queries and read the frame from HBM instead of the caller's copy (no per-call upload of ~64 KB);
- * other shapes return ORBFE_E_ARG (pass the host view). Valid until h's next extraction. */
+ * other shapes return ORBFE_E_ARG (pass the host view). Valid until h's next extraction.
+ * After orbfe_frame_rgbd the same pair of calls gives that frame's single-camera view: keys = the
+ * device mvKeysUn (undistorted), desc, uright = the device mvuRight from the depth image. */
 uint64_t orbfe_extractor_frame_id(orbfe_extractor* h);
 int orbfe_frame_device_view(orbfe_extractor* left, uint64_t frame_id, orbfe_frame* F);
 

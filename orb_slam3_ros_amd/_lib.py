@@ -32,6 +32,17 @@ class OrbKeyPoint(ctypes.Structure):
                 ("octave", ctypes.c_int32), ("class_id", ctypes.c_int32)]
 
 
+ORBFE_DEPTH_U16 = 0
+ORBFE_DEPTH_F32 = 1
+
+
+class RGBDParamsStruct(ctypes.Structure):
+    """orbfe_rgbd_params."""
+    _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("dist", ctypes.c_float * 12), ("ndist", ctypes.c_int32), ("bf", ctypes.c_float),
+                ("depth_factor", ctypes.c_float)]
+
+
 _c_int, _c_float, _vp = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 _P_int, _P_float = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float)
 
@@ -123,6 +134,9 @@ _SIGS = {
     "orbfe_keyframe_destroy": (None, [_vp]),
     "orbfe_keyframe_n": (_c_int, [_vp]),
     "orbfe_search_by_bow_batch": (_c_int, [_vp, _vp, _c_int, _vp, _vp, _vp, _vp, _c_float, _c_int]),
+    "orbfe_rgbd_stereo_batch": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp]),
+    "orbfe_frame_rgbd": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int,
+                                  _P_int, _vp, _vp]),
 }
 
 _lib = None

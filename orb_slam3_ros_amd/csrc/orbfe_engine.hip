@@ -93,6 +93,7 @@ struct orbfe_extractor {
     bool fused_pyramid_batch = ab_knob("ORBFE_FUSED_PYR_BATCH");  // A/B: k_pyramid for large batches too
     bool no_pull = ab_knob("ORBFE_NO_PULL");   // A/B: the frame call's results by DMA copies
     bool no_push = ab_knob("ORBFE_NO_PUSH");   // A/B: the frame call's images by a DMA copy
+    bool rgbd_mapped = ab_knob("ORBFE_RGBD_MAPPED");   // A/B: orbfe_frame_rgbd reads the depth image in place in mapped pinned memory
     int blur_variant = 0;
     std::vector<float> scale, inv_scale, sigma2, inv_sigma2;
     std::vector<int> per_level;
@@ -153,6 +154,18 @@ struct orbfe_extractor {
     uint64_t frame_id = 0, fs_id = 0;
     int fs_n = 0;
     float* d_scale = nullptr;
+    // orbfe_frame_rgbd (orbfe_rgbd.hip): its device results {mvKeysUn | mvuRight | mvDepth} for rg_kp
+    // slots (fs_rgbd: the frame fs_id names came from it, and the device view shows these), the depth
+    // staging of its DMA variant, and orbfe_rgbd_stereo_batch's depth pointer table
+    uint8_t* d_rg = nullptr;
+    float* d_rg_uright = nullptr;
+    int rg_kp = 0;
+    bool fs_rgbd = false;
+    uint8_t* d_rg_stage = nullptr;
+    size_t rg_stage_bytes = 0;
+    const void** d_rg_ptrs = nullptr;
+    int rg_ptrs_cap = 0;
+    std::vector<const void*> last_rg_ptrs;
     std::vector<const uint8_t*> last_ptrs;
     std::vector<int> last_laps;   // vLappingArea {lap0, lap1} per image of the last batch
     // stage timing
@@ -855,6 +868,9 @@ void orbfe_extractor_destroy(orbfe_extractor* h) {
     if (h->d_st) (void)hipFree(h->d_st);
     if (h->d_scale) (void)hipFree(h->d_scale);
     if (h->d_sdist) (void)hipFree(h->d_sdist);
+    if (h->d_rg) (void)hipFree(h->d_rg);
+    if (h->d_rg_stage) (void)hipFree(h->d_rg_stage);
+    if (h->d_rg_ptrs) (void)hipFree(h->d_rg_ptrs);
     for (int i = 0; i <= ORBFE_NUM_STAGES; i++)
         if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     for (int i = 0; i <= ORBFE_MAX_LEVELS; i++)
@@ -1338,6 +1354,7 @@ static int frame_pair(orbfe_extractor* left, orbfe_extractor* right, const uint8
     if (!fisheye) {   // the left image's records stay in the handle's output block (orbfe_frame_device_view)
         h->fs_id = h->frame_id;
         h->fs_n = cnt[0];
+        h->fs_rgbd = false;
     }
     const OrbKeyPoint* hk = (const OrbKeyPoint*)(hp + o_kps);
     const uint8_t* hd = hp + o_desc;
@@ -1385,7 +1402,8 @@ uint64_t orbfe_extractor_frame_id(orbfe_extractor* h) { return h ? h->frame_id :
 int orbfe_frame_device_view(orbfe_extractor* left, uint64_t frame_id, orbfe_frame* F) {
     if (!left || !F) return ORBFE_E_ARG;
     std::lock_guard<std::mutex> lk(left->mu);
-    if (frame_id == 0 || left->fs_id != frame_id || left->frame_id != frame_id || !left->last_kps || !left->d_st)
+    if (frame_id == 0 || left->fs_id != frame_id || left->frame_id != frame_id || !left->last_kps ||
+        !(left->fs_rgbd ? (void*)left->d_rg : (void*)left->d_st))
         return ORBFE_E_ARG;   // no frame call, or the handle has extracted since
     if (!left->d_scale) {
         HIPCHK(hipSetDevice(left->device));
@@ -1396,6 +1414,10 @@ int orbfe_frame_device_view(orbfe_extractor* left, uint64_t frame_id, orbfe_fram
     F->keys = (const orbfe_keypoint*)left->last_kps;   // image 0 of the last batch = the left image
     F->desc = left->last_desc;
     F->uright = left->d_uright;
+    if (left->fs_rgbd) {   // orbfe_frame_rgbd: mvKeysUn (undistorted) and the depth-derived mvuRight
+        F->keys = (const orbfe_keypoint*)left->d_rg;
+        F->uright = left->d_rg_uright;
+    }
     F->nlevels = left->nlevels;
     F->scale_factors = left->d_scale;
     F->two_cams = 0;
@@ -1497,3 +1519,6 @@ int orbfe_descriptor_distance(const uint8_t* a, const uint8_t* b) {
 
 // cv::remap INTER_LINEAR (stereo rectification before extraction).
 #include "orbfe_remap.hip"
+
+// The RGB-D Frame: UndistortKeyPoints + ComputeStereoFromRGBD after the extraction (uses undistort_point).
+#include "orbfe_rgbd.hip"

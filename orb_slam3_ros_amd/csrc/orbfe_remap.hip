@@ -171,11 +171,11 @@ struct UndistArgs {
     double fx, fy, cx, cy, ifx, ify;
     double k[12];
 };
-__global__ __launch_bounds__(256) void k_undistort(const float* __restrict__ in, int n, UndistArgs a, float* out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+// One point: (u, v) -> the undistorted pixel, shared by k_undistort and the RGB-D frame kernel
+// (orbfe_rgbd.hip) so both round alike.
+__device__ __forceinline__ void undistort_point(const UndistArgs& a, float in_x, float in_y, float& out_x, float& out_y) {
     const double* k = a.k;
-    double x = in[2 * i], y = in[2 * i + 1];
+    double x = in_x, y = in_y;
     const double u = x, v = y;
     x = (x - a.cx) * a.ifx;
     y = (y - a.cy) * a.ify;
@@ -202,8 +202,26 @@ __global__ __launch_bounds__(256) void k_undistort(const float* __restrict__ in,
     const double xx = a.fx * x + 0.0 * y + a.cx;
     const double yy = 0.0 * x + a.fy * y + a.cy;
     const double ww = 1. / (0.0 * x + 0.0 * y + 1.0);
-    out[2 * i] = (float)(xx * ww);
-    out[2 * i + 1] = (float)(yy * ww);
+    out_x = (float)(xx * ww);
+    out_y = (float)(yy * ww);
+}
+__global__ __launch_bounds__(256) void k_undistort(const float* __restrict__ in, int n, UndistArgs a, float* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float ox, oy;
+    undistort_point(a, in[2 * i], in[2 * i + 1], ox, oy);
+    out[2 * i] = ox;
+    out[2 * i + 1] = oy;
+}
+// K4 / dist (float, as mK / mDistCoef) widened to the kernel's doubles; coefficients past ndist are 0
+static UndistArgs undist_args(const float* K4, const float* dist, int ndist) {
+    UndistArgs a;
+    memset(&a, 0, sizeof(a));
+    a.fx = (double)K4[0]; a.fy = (double)K4[1]; a.cx = (double)K4[2]; a.cy = (double)K4[3];
+    a.ifx = 1. / a.fx;
+    a.ify = 1. / a.fy;
+    for (int i = 0; i < ndist; i++) a.k[i] = (double)dist[i];
+    return a;
 }
 
 extern "C" {
@@ -211,12 +229,7 @@ extern "C" {
 int orbfe_undistort_points(const float* pts, int n, const float* K4, const float* dist, int ndist, float* out) {
     if (n < 0 || (n > 0 && (!pts || !out)) || !K4 || (ndist > 0 && !dist) || ndist < 0 || ndist > 12) return ORBFE_E_ARG;
     if (n == 0) return 0;
-    UndistArgs a;
-    memset(&a, 0, sizeof(a));
-    a.fx = (double)K4[0]; a.fy = (double)K4[1]; a.cx = (double)K4[2]; a.cy = (double)K4[3];
-    a.ifx = 1. / a.fx;
-    a.ify = 1. / a.fy;
-    for (int i = 0; i < ndist; i++) a.k[i] = (double)dist[i];
+    const UndistArgs a = undist_args(K4, dist, ndist);
     Plan p;
     const size_t o_in = p.upload(pts, (size_t)n * 8);
     const size_t o_out = p.scratch((size_t)n * 8);

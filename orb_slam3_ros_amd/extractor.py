@@ -208,3 +208,63 @@ def frame_fisheye(left: ORBextractor, right: ORBextractor, imLeft, imRight, lap=
     return ((ml.value, kl[:n].copy(), dl[:n].copy()), (mr.value, kr[:m].copy(), dr[:m].copy()), l2r[:n].copy(),
             dist[:n].copy(), rc)
 
+
+
+class RGBDParams:
+    """orbfe_rgbd_params: K (fx, fy, cx, cy), DistCoef (0, 4, 5, 8 or 12 OpenCV coefficients), mbf and
+    mDepthMapFactor as Tracking holds it, already inverted (Tracking.cc:613-617: 1 / 5000 for TUM)."""
+
+    def __init__(self, fx: float, fy: float, cx: float, cy: float, dist=(), bf: float = 40.0,
+                 depth_factor: float = 1.0):
+        d = np.asarray(dist, np.float32).reshape(-1)
+        if len(d) not in (0, 4, 5, 8, 12):
+            raise _lib.OrbfeError("DistCoef has 0, 4, 5, 8 or 12 entries")
+        self.K4 = np.asarray([fx, fy, cx, cy], np.float32)
+        self.dist, self.bf, self.depth_factor = d, float(np.float32(bf)), float(np.float32(depth_factor))
+        self.c = _lib.RGBDParamsStruct(float(fx), float(fy), float(cx), float(cy), (ctypes.c_float * 12)(*d.tolist()),
+                                       len(d), float(bf), float(depth_factor))
+
+    def ref(self):
+        return ctypes.byref(self.c)
+
+
+def depth_type_of(imDepth) -> int:
+    """ORBFE_DEPTH_U16 / ORBFE_DEPTH_F32 from the array's dtype (imDepth.type() in the shim)."""
+    if imDepth.dtype == np.uint16:
+        return _lib.ORBFE_DEPTH_U16
+    if imDepth.dtype == np.float32:
+        return _lib.ORBFE_DEPTH_F32
+    raise _lib.OrbfeError("the depth image is uint16 (CV_16UC1) or float32 (CV_32FC1)")
+
+
+def frame_rgbd(ext: ORBextractor, imGray, imDepth, params: RGBDParams):
+    """Frame::Frame(imGray, imDepth, ...) (Frame.cc:222-237) in one library call: ExtractORB(0, imGray,
+    0, 0), UndistortKeyPoints and ComputeStereoFromRGBD over the RAW depth image (GrabImageRGBD's
+    convertTo happens at the keypoints). Rows of either image may be strided. Returns (mvKeys,
+    mvKeysUn, mDescriptors, mvuRight, mvDepth)."""
+    g, d = np.asarray(imGray), np.asarray(imDepth)
+    if g.size == 0:
+        return (np.zeros(0, KEYPOINT_DTYPE), np.zeros(0, KEYPOINT_DTYPE), np.zeros((0, 32), np.uint8),
+                np.zeros(0, np.float32), np.zeros(0, np.float32))
+    if g.dtype != np.uint8 or g.ndim != 2:
+        raise _lib.OrbfeError("ORBextractor expects a single-channel uint8 image (CV_8UC1)")
+    dt = depth_type_of(d)
+    if d.ndim != 2 or d.shape != g.shape:
+        raise _lib.OrbfeError("the depth image has the gray image's size")
+    if g.strides[1] != 1 or g.strides[0] < g.shape[1]:
+        g = np.ascontiguousarray(g)
+    if d.strides[1] != d.itemsize or d.strides[0] < d.shape[1] * d.itemsize:
+        d = np.ascontiguousarray(d)
+    h, w = g.shape
+    cap = ext.capacity(w, h)
+    kps, kun = np.zeros(cap, KEYPOINT_DTYPE), np.zeros(cap, KEYPOINT_DTYPE)
+    desc = np.zeros((cap, 32), np.uint8)
+    ur, dp = np.zeros(cap, np.float32), np.zeros(cap, np.float32)
+    n = ctypes.c_int()
+    rc = _lib.load().orbfe_frame_rgbd(ext.handle, g.ctypes.data, w, h, g.strides[0], d.ctypes.data, dt, d.strides[0],
+                                      params.ref(), kps.ctypes.data, kun.ctypes.data, desc.ctypes.data, cap,
+                                      ctypes.byref(n), ur.ctypes.data, dp.ctypes.data)
+    _lib.check(rc, "orbfe_frame_rgbd")
+    ext._last_shape = (h, w)
+    k = n.value
+    return kps[:k].copy(), kun[:k].copy(), desc[:k].copy(), ur[:k].copy(), dp[:k].copy()

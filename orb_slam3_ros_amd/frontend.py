@@ -200,3 +200,69 @@ class StereoFrontEnd:
                 self.lib.orbfe_extractor_destroy(h)
         self.handles = []
         self.h = None
+
+
+class RGBDFrontEnd:
+    """Batched device RGB-D front end: orbfe_extract_batch over F gray images, then
+    orbfe_rgbd_stereo_batch over their F depth images (the batched form of Frame::Frame(imGray,
+    imDepth, ...), Frame.cc:222-237). Outputs are device tensors padded to `cap`: kps / desc / counts as
+    StereoFrontEnd's, keys_un (mvKeysUn records), uright and depth (mvuRight, mvDepth; slots at or past
+    an image's count keep their previous contents)."""
+
+    def __init__(self, frames: int, width: int, height: int, params, nfeatures: int = 1000, scale_factor: float = 1.2,
+                 nlevels: int = 8, ini_th: int = 20, min_th: int = 7, device=None):
+        import torch
+        self.torch, self.lib, self.params = torch, _lib.load(), params
+        self.F, self.W, self.H = int(frames), int(width), int(height)
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        h = ctypes.c_void_p()
+        _lib.check(self.lib.orbfe_extractor_create(nfeatures, scale_factor, nlevels, ini_th, min_th, ctypes.byref(h)),
+                   "create")
+        self.h = h
+        self.cap = _lib.check(self.lib.orbfe_extractor_capacity(h, self.W, self.H), "capacity")
+        t, n = torch, self.F
+        self.kps = t.zeros((n, self.cap, 7), dtype=t.int32, device=self.device)
+        self.desc = t.zeros((n, self.cap, 32), dtype=t.uint8, device=self.device)
+        self.counts = t.zeros((n, 2), dtype=t.int32, device=self.device)
+        self.keys_un = t.zeros((n, self.cap, 7), dtype=t.int32, device=self.device)
+        self.uright = t.zeros((n, self.cap), dtype=t.float32, device=self.device)
+        self.depth = t.zeros((n, self.cap), dtype=t.float32, device=self.device)
+        _lib.check(self.lib.orbfe_set_batch_outputs(h, self.kps.data_ptr(), self.desc.data_ptr(),
+                                                    self.counts.data_ptr(), n), "set_batch_outputs")
+
+    def run(self, images, depths):
+        """images: [F, H, W] uint8, depths: [F, H, W] uint16 or float32 (raw depth), device tensors with
+        contiguous pixels in a row. Runs on the caller's current torch stream. Returns (uright, depth,
+        keys_un)."""
+        torch = self.torch
+        assert images.dtype == torch.uint8 and images.is_cuda and tuple(images.shape) == (self.F, self.H, self.W)
+        assert depths.is_cuda and tuple(depths.shape) == (self.F, self.H, self.W)
+        assert images.stride(2) == 1 and depths.stride(2) == 1, (images.stride(), depths.stride())
+        if depths.dtype == torch.float32:
+            dt = _lib.ORBFE_DEPTH_F32
+        elif depths.dtype in (torch.uint16, torch.int16):   # int16: a reinterpreted CV_16U buffer
+            dt = _lib.ORBFE_DEPTH_U16
+        else:
+            raise _lib.OrbfeError("the depth tensor is uint16 (CV_16UC1) or float32 (CV_32FC1)")
+        s = torch.cuda.current_stream(self.device).cuda_stream
+        ip = (ctypes.c_void_p * self.F)(*[images[i].data_ptr() for i in range(self.F)])
+        dptr = (ctypes.c_void_p * self.F)(*[depths[i].data_ptr() for i in range(self.F)])
+        _lib.check(self.lib.orbfe_extract_batch(self.h, self.F, ip, self.W, self.H, images.stride(1), 0, 0, s),
+                   "extract_batch")
+        _lib.check(self.lib.orbfe_rgbd_stereo_batch(self.h, 0, 1, self.F, dptr, dt,
+                                                    depths.stride(1) * depths.element_size(), self.params.ref(),
+                                                    self.keys_un.data_ptr(), self.uright.data_ptr(),
+                                                    self.depth.data_ptr(), s), "rgbd_stereo_batch")
+        return self.uright, self.depth, self.keys_un
+
+    def host_frame(self, f: int):
+        """(mvKeys, mvKeysUn, mDescriptors, mvuRight, mvDepth) of frame f, copied to the host."""
+        n = int(self.counts[f, 0].cpu())
+        kp = self.kps[f, :n].cpu().numpy().view(KEYPOINT_DTYPE).reshape(n)
+        ku = self.keys_un[f, :n].cpu().numpy().view(KEYPOINT_DTYPE).reshape(n)
+        return kp, ku, self.desc[f, :n].cpu().numpy(), self.uright[f, :n].cpu().numpy(), self.depth[f, :n].cpu().numpy()
+
+    def close(self):
+        if self.h:
+            self.lib.orbfe_extractor_destroy(self.h)
+            self.h = None

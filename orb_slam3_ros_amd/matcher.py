@@ -743,8 +743,9 @@ def stereo_knn_ratio(left_desc, right_desc, ratio: float = 0.7):
 
 
 def current_frame_view(F: MatchFrame, left, frame_id: int):
-    """The device view (orbfe_frame_device_view) of the frame the last orbfe_frame_stereo on extractor
-    `left` produced, with F's bounds and mbf: a CFrame whose keys / desc / uR / scale factors are in
+    """The device view (orbfe_frame_device_view) of the frame the last orbfe_frame_stereo or
+    orbfe_frame_rgbd (then keys = mvKeysUn, uR from the depth image) on extractor `left` produced, with
+    F's bounds and mbf: a CFrame whose keys / desc / uR / scale factors are in
     HBM, for the host-API single-camera searches (SearchByProjectionLocalMap / LastFrame /
     search_local_points take it through MatchFrame-compatible `.ref()`). None when stale."""
     c = CFrame()

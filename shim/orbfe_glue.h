@@ -95,6 +95,57 @@ int frame_fisheye(orbfe_extractor* hl, orbfe_extractor* hr, const uint8_t* img_l
     return ng;
 }
 
+// Frame::Frame(imGray, imDepth, ...) (Frame.cc:222-237): ExtractORB(0, imGray, 0, 0), UndistortKeyPoints
+// and ComputeStereoFromRGBD as ONE orbfe_frame_rgbd call over the RAW depth image (depth_type
+// ORBFE_DEPTH_U16 / ORBFE_DEPTH_F32 from imDepth.type(); GrabImageRGBD's convertTo happens at the
+// keypoints inside the call). Key / Desc as frame_stereo. On success keys / keys_un / ur / depth hold
+// mvKeys, mvKeysUn, mvuRight, mvDepth (-1 = no depth) and the return value is operator()'s monoIndex.
+// An empty image gives no keypoints and returns -1, as operator() (ORBextractor.cc:1090-1091); any
+// other negative return is a library status and the caller then runs the reference's body.
+template <class Key, class Desc>
+int frame_rgbd(orbfe_extractor* h, const uint8_t* img, int width, int height, int stride, const void* depth,
+               int depth_type, int depth_stride_bytes, const orbfe_rgbd_params& p, std::vector<Key>& keys,
+               std::vector<Key>& keys_un, Desc& desc, std::vector<float>& ur, std::vector<float>& depth_out) {
+    static_assert(sizeof(Key) == sizeof(orbfe_keypoint), "cv::KeyPoint layout (28 B) expected");
+    if (width <= 0 || height <= 0 || !img) {
+        keys.clear(); keys_un.clear(); ur.clear(); depth_out.clear();
+        desc.keep(0);
+        return ORBFE_E_EMPTY;
+    }
+    const int cap = orbfe_extractor_capacity(h, width, height);
+    if (cap < 0) return cap;
+    keys.resize(cap);
+    keys_un.resize(cap);
+    ur.resize(cap);
+    depth_out.resize(cap);
+    int n = 0;
+    const int mono = orbfe_frame_rgbd(h, img, width, height, stride, depth, depth_type, depth_stride_bytes, &p,
+                                      reinterpret_cast<orbfe_keypoint*>(keys.data()),
+                                      reinterpret_cast<orbfe_keypoint*>(keys_un.data()), desc.rows(cap), cap, &n,
+                                      ur.data(), depth_out.data());
+    if (mono < 0) n = 0;
+    keys.resize(n);
+    keys_un.resize(n);
+    desc.keep(n);
+    ur.resize(n);
+    depth_out.resize(n);
+    return mono;
+}
+
+// mK / mDistCoef / mbf / mDepthMapFactor as orbfe_frame_rgbd reads them: dist = the ndist (0, 4, 5, 8
+// or 12) coefficients of mDistCoef, depth_factor = Tracking's mDepthMapFactor (already inverted).
+inline orbfe_rgbd_params rgbd_params(float fx, float fy, float cx, float cy, const float* dist, int ndist, float bf,
+                                     float depth_factor) {
+    orbfe_rgbd_params p;
+    memset(&p, 0, sizeof(p));
+    p.fx = fx; p.fy = fy; p.cx = cx; p.cy = cy;
+    for (int i = 0; i < ndist && i < 12; i++) p.dist[i] = dist[i];
+    p.ndist = ndist;
+    p.bf = bf;
+    p.depth_factor = depth_factor;
+    return p;
+}
+
 // The pose part of Frame::isInFrustum's inputs (Frame.cc:512-586): Rcw row-major, tcw, Ow = the
 // camera centre; fx..cy the pinhole parameters (unused with a rig), mfLogScaleFactor, and the
 // viewing-cosine limit SearchLocalPoints passes (0.5, Tracking.cc:3415).
