@@ -3619,6 +3619,114 @@ template <typename T> T* ms_ptr(size_t off) { return reinterpret_cast<T*>(t_ms.d
 // an uploaded input: the device arena copy, or (zero copy) the mapped pinned staging itself
 template <typename T> T* up_ptr(size_t off, bool zc) { return reinterpret_cast<T*>((zc ? t_ms.hd : t_ms.d) + off); }
 
+// ---- the drivers' shared plumbing. All of it reads t_ms when called, never across ms_prepare (which
+// resets the scratch on a device switch). ----
+#define MSCHK(x)                   \
+    do {                           \
+        const int rc_ = (x);       \
+        if (rc_) return rc_;       \
+    } while (0)
+
+// Device-resident call (the *_device entry points): F's arrays, mvp, mvp_obs and the query
+// records are device pointers produced on `caller`; the search runs on that stream, results are
+// written in place and the call returns once its status words are published.
+struct DevIn {
+    hipStream_t caller;
+};
+// The stream a driver works on: a device-resident call's own, ordered here after the thread's
+// previous device-resident search (MatchScratch::tail), else the thread's matcher stream (which
+// ms_prepare ordered after it).
+inline int ms_call_stream(const DevIn* dev, hipStream_t& s) {
+    s = dev ? dev->caller : t_ms.stream;
+    if (dev) HIPCHK(ms_after_tail(s));
+    return ORBFE_OK;
+}
+// After a device-resident call's last launch (and before timer.end()): the event the next call of
+// this thread orders itself after (MatchScratch::tail). Host-API calls end with the stream drained
+// or their one launch awaited, and record nothing.
+inline int ms_record_tail(const DevIn* dev, hipStream_t s) {
+    if (!dev) return ORBFE_OK;
+    HIPCHK(hipEventRecord(t_ms.tail, s));
+    t_ms.tail_stream = s;
+    return ORBFE_OK;
+}
+
+// The zero-copy status hand-off, host side (host_seq_acquire): spin until a commit kernel on stream s
+// has published sequence number seq in the status words. Bounded: a stream that finished without
+// publishing is ORBFE_E_DEVICE. On ORBFE_OK the slots and t_ms.hs[0..5] of that commit are visible.
+inline int ms_wait_seq(hipStream_t s, int seq) {
+    volatile int* st = t_ms.hs;
+    for (unsigned spin = 1; host_seq_acquire(st) != seq; spin++) {
+        if ((spin & 1023) == 0) {
+            const hipError_t e = hipStreamQuery(s);
+            if (e == hipSuccess && host_seq_acquire(st) != seq) return ORBFE_E_DEVICE;
+            if (e != hipSuccess && e != hipErrorNotReady) HIPCHK(e);
+        }
+        __builtin_ia32_pause();
+    }
+    return ORBFE_OK;
+}
+
+// The mapped pinned slot block (MatchScratch::ho / ho_dev) holds at least `words` ints; a block that
+// is too small is replaced by one of grow_to
+inline int ms_out_block(size_t words, size_t grow_to) {
+    MatchScratch& m = t_ms;
+    if (m.ocap >= words) return ORBFE_OK;
+    if (m.ho) HIPCHK(hipHostFree(m.ho));
+    m.ho = nullptr;
+    m.ocap = 0;
+    HIPCHK(hipHostMalloc((void**)&m.ho, grow_to * 4, hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCHK(hipHostGetDevicePointer((void**)&m.ho_dev, m.ho, 0));
+    m.ocap = grow_to;
+    return ORBFE_OK;
+}
+
+// One device int through the pinned status words (a pageable 4-byte read back costs more than the
+// kernels it follows). Copies queued on s before it complete under the same synchronisation.
+inline int ms_read_int(const int* d, hipStream_t s, int& out) {
+    HIPCHK(hipMemcpyAsync(t_ms.hs, d, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    out = t_ms.hs[0];
+    return ORBFE_OK;
+}
+
+// Counting mode (orbfe_matcher_set_stats). The three device words are planned with the call's other
+// scratch (stats_plan, before ms_prepare); begin(), once the call's stream is known, forgets the
+// previous search's counts and zeroes the words on that stream.
+inline size_t stats_plan(Plan& p) { return t_stats ? p.scratch(24) : 0; }
+struct StatsScope {
+    unsigned long long* words = nullptr;   // the kernels' stats argument (NULL: not counting)
+    [[nodiscard]] int begin(size_t off, hipStream_t s) {
+        t_last_stats[0] = t_last_stats[1] = t_last_stats[2] = -1;
+        if (!t_stats) return ORBFE_OK;
+        words = ms_ptr<unsigned long long>(off);
+        HIPCHK(hipMemsetAsync(words, 0, 24, s));
+        return ORBFE_OK;
+    }
+    // counting mode only: one more copy and synchronisation. cand: the device word reported as window
+    // candidates; passes: the pass count when the host knows it (< 0: device word 2)
+    int read(hipStream_t s, int cand = 0, long long passes = -1) const {
+        if (!words) return ORBFE_OK;
+        unsigned long long hst[3];
+        HIPCHK(hipMemcpyAsync(hst, words, 24, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        t_last_stats[0] = (long long)hst[cand];
+        t_last_stats[1] = (long long)hst[1];
+        t_last_stats[2] = passes >= 0 ? passes : (long long)hst[2];
+        return ORBFE_OK;
+    }
+};
+
+// The query records' layout: byte stride and the offsets of the fields the drivers address
+struct RecLayout {
+    int stride, obs_off, id_off, angle_off, level_off;
+};
+constexpr RecLayout kMapPointRec{(int)sizeof(orbfe_map_point), (int)offsetof(orbfe_map_point, observations),
+                                 (int)offsetof(orbfe_map_point, id), 0, (int)offsetof(orbfe_map_point, scale_level)};
+constexpr RecLayout kProjPointRec{(int)sizeof(orbfe_proj_point), (int)offsetof(orbfe_proj_point, observations),
+                                  (int)offsetof(orbfe_proj_point, id), (int)offsetof(orbfe_proj_point, angle),
+                                  (int)offsetof(orbfe_proj_point, octave)};
+
 // Upload a frame and plan its grid; returns the device view after ms_prepare (fill_frame).
 struct FramePlan {
     const orbfe_frame* F;
@@ -3784,12 +3892,22 @@ bool make_camdev(const orbfe_frame* F, const orbfe_camera* cam, const orbfe_ster
     return true;
 }
 
-// Device-resident call (the *_device entry points): F's arrays, mvp, mvp_obs and the query
-// records are device pointers produced on `caller`; the matcher's stream waits for it, results
-// are written in place and the call returns after they are complete.
-struct DevIn {
-    hipStream_t caller;
-};
+// Tracking::SearchLocalPoints' isInFrustum on stream s: nq world points at pts (device) to map point
+// records in the arena at o_track (and fin.track_dev), their count in ntm (zeroed here). The search
+// that follows reads those records: q and its layout are rebound to them. ORBFE_E_ARG: bad camera.
+inline int frustum_stage(const orbfe_frame* F, const FrustumIn& fin, const void* pts, int nq, size_t o_track, int* ntm,
+                         hipStream_t s, const uint8_t*& q, RecLayout& rl) {
+    CamDev cd;
+    if (!make_camdev(F, fin.cam, fin.rig, cd)) return ORBFE_E_ARG;
+    HIPCHK(hipMemsetAsync(ntm, 0, 4, s));
+    hipLaunchKernelGGL(k_frustum, dim3((nq + MT_NT - 1) / MT_NT), dim3(MT_NT), 0, s, cd, (const orbfe_map_point_3d*)pts,
+                       nq, ms_ptr<orbfe_map_point>(o_track), ntm, fin.track_dev);
+    t_ms.last_track = ms_ptr<const orbfe_map_point>(o_track);
+    t_ms.last_track_n = nq;
+    q = ms_ptr<const uint8_t>(o_track);
+    rl = kMapPointRec;
+    return ORBFE_OK;
+}
 
 // k_sbp_block's bucket geometry for a frame: bands of 16 rows, then as many column strips (<= 32, >= 24
 // columns wide) as 8192 buckets and the LDS allow; false: the frame does not fit the block form
@@ -3816,78 +3934,56 @@ bool blk_geom(const orbfe_frame* F, BlkGeom& gm, int ncam = 1, int bpk = 61) {
 // anything; the caller runs the multi-launch form.
 constexpr int kBlockAborted = -1000;
 int sbp_block_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs, const void* queries, int nq,
-                  size_t qstride, size_t qid_off, size_t qangle_off, float th, int a0, int a1, float thFar,
-                  float nnratio, int maxDist, int checkOri, const BlkGeom& gm, const FrustumIn* fin, const DevIn* dev,
+                  const RecLayout& layout, float th, int a0, int a1, float thFar, float nnratio, int maxDist,
+                  int checkOri, const BlkGeom& gm, const FrustumIn* fin, const DevIn* dev,
                   const LastProjIn* lp = nullptr) {
     const int n = F->n;
+    RecLayout rl = layout;
     Plan p;
     FramePlan fp;
     if (dev || F->device) fp.plan_dev(F, mode != 2);   // a device frame: read in place
     else fp.plan(p, F, true, mode != 2);
     const size_t o_q = dev ? 0 : fin ? p.upload(fin->pts, (size_t)nq * sizeof(orbfe_map_point_3d))
                                      : lp ? p.upload(lp->pts, (size_t)nq * sizeof(orbfe_last_point))
-                                          : p.upload(queries, (size_t)nq * qstride);
+                                          : p.upload(queries, (size_t)nq * rl.stride);
     const size_t o_rec = lp ? p.scratch((size_t)nq * sizeof(orbfe_proj_point)) : 0;   // device-projected records
     const size_t o_mvp = dev ? 0 : p.upload(mvp, (size_t)n * 4);
     const size_t o_obs = (dev || mode == 2) ? 0 : p.upload(mvp_obs, (size_t)n * 4);
     const size_t o_track = fin ? p.scratch((size_t)nq * sizeof(orbfe_map_point)) : 0;
     const size_t o_ntm = fin ? p.scratch(16) : 0;
-    const size_t o_stats = t_stats ? p.scratch(24) : 0;
-#ifndef ORBFE_BLK_DMA
-#define ORBFE_BLK_DMA 0
-#endif
+    const size_t o_stats = stats_plan(p);
     // host-API calls: zero copy both ways. The kernel reads its inputs straight from the mapped pinned
     // staging and writes the slots into mapped pinned memory; the host waits for the status words
-    // only (no DMA, no stream synchronisation: the call is one launch). (ORBFE_BLK_DMA: inputs by one
-    // DMA instead, an A/B build.)
-    const bool zc = !dev, zin = zc && !ORBFE_BLK_DMA;
-    const size_t o_qdev = (!dev && !fin && !lp && zin) ? p.scratch((size_t)nq * qstride) : 0;
-    int rc = ms_prepare(p, zin);
-    if (rc) return rc;
+    // only (no DMA, no stream synchronisation: the call is one launch). Inputs by one DMA instead
+    // measured slower (profiles/r06_kernel_ab.txt item 24).
+    const bool zc = !dev;
+    const size_t o_qdev = (zc && !fin && !lp) ? p.scratch((size_t)nq * rl.stride) : 0;
+    MSCHK(ms_prepare(p, zc));
+    if (zc) MSCHK(ms_out_block((size_t)n, std::max<size_t>((size_t)n, 2048)));
     MatchScratch& m = t_ms;
-    if (zc && m.ocap < (size_t)n) {
-        if (m.ho) HIPCHK(hipHostFree(m.ho));
-        m.ho = nullptr;
-        m.ocap = 0;
-        const size_t cap = std::max<size_t>((size_t)n, 2048);
-        HIPCHK(hipHostMalloc((void**)&m.ho, cap * 4, hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostGetDevicePointer((void**)&m.ho_dev, m.ho, 0));
-        m.ocap = cap;
-    }
-    fp.zc = zin;
-    hipStream_t s = dev ? dev->caller : t_ms.stream;
-    if (dev) HIPCHK(ms_after_tail(s));
-    unsigned long long* stats = t_stats ? ms_ptr<unsigned long long>(o_stats) : nullptr;
-    t_last_stats[0] = t_last_stats[1] = t_last_stats[2] = -1;
-    if (stats) HIPCHK(hipMemsetAsync(stats, 0, 24, s));
+    fp.zc = zc;
+    hipStream_t s;
+    MSCHK(ms_call_stream(dev, s));
+    StatsScope stats;
+    MSCHK(stats.begin(o_stats, s));
     MsTimer timer(s);
     const FrameDev fr = fp.view();
-    const uint8_t* q = dev ? (const uint8_t*)(fin ? (const void*)fin->pts : queries) : up_ptr<const uint8_t>(o_q, zin);
+    const uint8_t* q = dev ? (const uint8_t*)(fin ? (const void*)fin->pts : queries) : up_ptr<const uint8_t>(o_q, zc);
     int* ntm = fin ? ms_ptr<int>(o_ntm) : nullptr;
-    if (fin) {   // Tracking::SearchLocalPoints' isInFrustum, then the search (nothing in view: no match)
-        CamDev cd;
-        if (!make_camdev(F, fin->cam, fin->rig, cd)) return ORBFE_E_ARG;
-        HIPCHK(hipMemsetAsync(ntm, 0, 4, s));
-        hipLaunchKernelGGL(k_frustum, dim3((nq + MT_NT - 1) / MT_NT), dim3(MT_NT), 0, s, cd,
-                           (const orbfe_map_point_3d*)q, nq, ms_ptr<orbfe_map_point>(o_track), ntm, fin->track_dev);
-        t_ms.last_track = ms_ptr<const orbfe_map_point>(o_track);
-        t_ms.last_track_n = nq;
-        q = ms_ptr<const uint8_t>(o_track);
-        qstride = sizeof(orbfe_map_point);
-        qid_off = offsetof(orbfe_map_point, id);
-    }
+    // Tracking::SearchLocalPoints' isInFrustum, then the search (nothing in view: no match)
+    if (fin) MSCHK(frustum_stage(F, *fin, q, nq, o_track, ntm, s, q, rl));
     if (lp) {   // SearchByProjection(CurrentFrame, LastFrame)'s projection on the device
         hipLaunchKernelGGL(k_last_proj, dim3((nq + MT_NT - 1) / MT_NT), dim3(MT_NT), 0, s, *lp,
-                           up_ptr<const orbfe_last_point>(o_q, zin), nq, ms_ptr<orbfe_proj_point>(o_rec), (float2*)nullptr);
+                           up_ptr<const orbfe_last_point>(o_q, zc), nq, ms_ptr<orbfe_proj_point>(o_rec), (float2*)nullptr);
         q = ms_ptr<const uint8_t>(o_rec);
     }
-    const int32_t* mvp_in = dev ? mvp : up_ptr<const int32_t>(o_mvp, zin);
+    const int32_t* mvp_in = dev ? mvp : up_ptr<const int32_t>(o_mvp, zc);
     int32_t* mvp_out = dev ? mvp : m.ho_dev;
-    const int32_t* obs_d = mode == 2 ? nullptr : dev ? mvp_obs : up_ptr<const int32_t>(o_obs, zin);
+    const int32_t* obs_d = mode == 2 ? nullptr : dev ? mvp_obs : up_ptr<const int32_t>(o_obs, zc);
     const int seq = ++t_ms.seq;
     if (zc) memcpy(m.ho, mvp, (size_t)n * 4);   // the slots the search leaves alone keep their value
-    const BlkIO io{mvp_in, obs_d, mvp_out, (int)qstride, (int)qid_off, (int)qangle_off, checkOri, ntm, t_ms.hs_dev, seq,
-                   stats, (!dev && !fin && !lp && zin) ? ms_ptr<uint4>(o_qdev) : nullptr};
+    const BlkIO io{mvp_in, obs_d, mvp_out, rl.stride, rl.id_off, rl.angle_off, checkOri, ntm, t_ms.hs_dev, seq,
+                   stats.words, (zc && !fin && !lp) ? ms_ptr<uint4>(o_qdev) : nullptr};
     const bool two4 = F->two_cams && mode == 0;
     const size_t lds = two4 ? blk_lds(n, F->nlevels, gm, 2, blk4_bytes_per_kp()) : blk_lds(n, F->nlevels, gm);
     if (two4)
@@ -3903,31 +3999,14 @@ int sbp_block_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* m
         hipLaunchKernelGGL(k_sbp_block<2>, dim3(1), dim3(MT_BLK_NT), lds, s, fr, gm, (const void*)q, nq, th, a0, a1,
                            thFar, nnratio, maxDist, 0, io);
     HIPCHK(hipGetLastError());
-    if (dev) {
-        HIPCHK(hipEventRecord(t_ms.tail, s));
-        t_ms.tail_stream = s;
-    }
+    MSCHK(ms_record_tail(dev, s));
     timer.end();
+    MSCHK(ms_wait_seq(s, seq));
     volatile int* st = t_ms.hs;
-    for (unsigned spin = 1; host_seq_acquire(st) != seq; spin++) {
-        if ((spin & 1023) == 0) {   // bounded: a stream that finished without publishing is an error
-            const hipError_t e = hipStreamQuery(s);
-            if (e == hipSuccess && host_seq_acquire(st) != seq) return ORBFE_E_DEVICE;
-            if (e != hipSuccess && e != hipErrorNotReady) HIPCHK(e);
-        }
-        __builtin_ia32_pause();
-    }
     if (st[0] == 2) return kBlockAborted;   // k_sbp_block4: a slot with too many writers, nothing written
     if (zc) memcpy(mvp, m.ho, (size_t)n * 4);   // complete: the status words come after the slot writes
     if (fin && fin->n_to_match) *fin->n_to_match = st[5];
-    if (stats) {   // counting mode only: one more copy and synchronisation
-        unsigned long long hst[3];
-        HIPCHK(hipMemcpyAsync(hst, stats, 24, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        t_last_stats[0] = (long long)hst[0];
-        t_last_stats[1] = (long long)hst[1];
-        t_last_stats[2] = (long long)hst[2];
-    }
+    MSCHK(stats.read(s));
     return st[1] - st[2];
 }
 
@@ -3947,33 +4026,22 @@ int sbp_block2_run(const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs, c
     const size_t o_rec = lp ? p.scratch((size_t)nq * sizeof(orbfe_proj_point)) : 0;
     const size_t o_mvp = p.upload(mvp, (size_t)n * 4);
     const size_t o_obs = p.upload(mvp_obs, (size_t)n * 4);
-    const size_t o_stats = t_stats ? p.scratch(24) : 0;
+    const size_t o_stats = stats_plan(p);
     const size_t o_qdev = lp ? 0 : p.scratch((size_t)nq * sizeof(orbfe_proj_point));
-    int rc = ms_prepare(p, true);
-    if (rc) return rc;
+    MSCHK(ms_prepare(p, true));
+    MSCHK(ms_out_block((size_t)n, std::max<size_t>((size_t)n, 2048)));
     MatchScratch& m = t_ms;
-    if (m.ocap < (size_t)n) {
-        if (m.ho) HIPCHK(hipHostFree(m.ho));
-        m.ho = nullptr;
-        m.ocap = 0;
-        const size_t cap = std::max<size_t>((size_t)n, 2048);
-        HIPCHK(hipHostMalloc((void**)&m.ho, cap * 4, hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostGetDevicePointer((void**)&m.ho_dev, m.ho, 0));
-        m.ocap = cap;
-    }
     fp.zc = true;
     hipStream_t s = t_ms.stream;
-    unsigned long long* stats = t_stats ? ms_ptr<unsigned long long>(o_stats) : nullptr;
-    t_last_stats[0] = t_last_stats[1] = t_last_stats[2] = -1;
-    if (stats) HIPCHK(hipMemsetAsync(stats, 0, 24, s));
+    StatsScope stats;
+    MSCHK(stats.begin(o_stats, s));
     MsTimer timer(s);
     const FrameDev fr = fp.view();
     const int seq = ++t_ms.seq;
     memcpy(m.ho, mvp, (size_t)n * 4);   // the slots the search leaves alone keep their value
     const BlkIO io{up_ptr<const int32_t>(o_mvp, true), up_ptr<const int32_t>(o_obs, true), m.ho_dev,
-                   (int)sizeof(orbfe_proj_point), (int)offsetof(orbfe_proj_point, id),
-                   (int)offsetof(orbfe_proj_point, angle), checkOri, nullptr, t_ms.hs_dev, seq, stats,
-                   lp ? nullptr : ms_ptr<uint4>(o_qdev)};
+                   kProjPointRec.stride, kProjPointRec.id_off, kProjPointRec.angle_off, checkOri, nullptr, t_ms.hs_dev,
+                   seq, stats.words, lp ? nullptr : ms_ptr<uint4>(o_qdev)};
     const orbfe_proj_point* recs = up_ptr<const orbfe_proj_point>(o_q, true);
     const float2* ruv = up_ptr<const float2>(o_ruv, true);
     if (lp) {   // the projection into both cameras on the device; records and right centres in HBM
@@ -3987,24 +4055,10 @@ int sbp_block2_run(const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs, c
                        th, a0, a1, maxDist, io);
     HIPCHK(hipGetLastError());
     timer.end();
+    MSCHK(ms_wait_seq(s, seq));
     volatile int* st = t_ms.hs;
-    for (unsigned spin = 1; host_seq_acquire(st) != seq; spin++) {
-        if ((spin & 1023) == 0) {   // bounded: a stream that finished without publishing is an error
-            const hipError_t e = hipStreamQuery(s);
-            if (e == hipSuccess && host_seq_acquire(st) != seq) return ORBFE_E_DEVICE;
-            if (e != hipSuccess && e != hipErrorNotReady) HIPCHK(e);
-        }
-        __builtin_ia32_pause();
-    }
     memcpy(mvp, m.ho, (size_t)n * 4);
-    if (stats) {
-        unsigned long long hst[3];
-        HIPCHK(hipMemcpyAsync(hst, stats, 24, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        t_last_stats[0] = (long long)hst[0];
-        t_last_stats[1] = (long long)hst[1];
-        t_last_stats[2] = (long long)hst[2];
-    }
+    MSCHK(stats.read(s));
     return st[1] - st[2];
 }
 
@@ -4027,16 +4081,17 @@ size_t multi_lds(int n, int nlev, const BlkGeom& gm) {
 // sbp_run's multi-block form for single-camera local-map searches of more than MT_BLOCK_MAXQ points
 // (k_sbp_multi0 / k_sbp_multi): arguments already validated by sbp_run.
 int sbp_multi_run(const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs, const void* queries, int nq,
-                  size_t qstride, size_t qid_off, float th, int a0, float thFar, float nnratio, const BlkGeom& gm,
+                  const RecLayout& layout, float th, int a0, float thFar, float nnratio, const BlkGeom& gm,
                   const FrustumIn* fin, const DevIn* dev) {
     const int n = F->n;
     const int nbk = F->nlevels * gm.NB * gm.NS;
+    RecLayout rl = layout;
     Plan p;
     FramePlan fp;
     if (dev) fp.plan_dev(F, true);
     else fp.plan(p, F, true, true);
     const size_t o_q = dev ? 0 : fin ? p.upload(fin->pts, (size_t)nq * sizeof(orbfe_map_point_3d))
-                                     : p.upload(queries, (size_t)nq * qstride);
+                                     : p.upload(queries, (size_t)nq * rl.stride);
     const size_t o_mvp = dev ? 0 : p.upload(mvp, (size_t)n * 4);
     const size_t o_obs = dev ? 0 : p.upload(mvp_obs, (size_t)n * 4);
     const size_t o_track = fin ? p.scratch((size_t)nq * sizeof(orbfe_map_point)) : 0;
@@ -4049,12 +4104,11 @@ int sbp_multi_run(const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs, co
     const size_t o_gdesc = p.scratch((size_t)n * 32);
     const size_t o_gbe = p.scratch((size_t)(nbk + 1) * 4);
     const size_t o_gblk = p.scratch((size_t)n);
-    const size_t o_stats = t_stats ? p.scratch(24) : 0;
-    int rc = ms_prepare(p);
-    if (rc) return rc;
+    const size_t o_stats = stats_plan(p);
+    MSCHK(ms_prepare(p));
     MatchScratch& m = t_ms;
-    hipStream_t s = dev ? dev->caller : m.stream;
-    if (dev) HIPCHK(ms_after_tail(s));
+    hipStream_t s;
+    MSCHK(ms_call_stream(dev, s));
     if (!m.mbuf) {   // zeroed on the search's stream (a non-blocking stream does not wait for the null stream)
         HIPCHK(hipMalloc(&m.mbuf, MultiBuf::bytes));
         HIPCHK(hipMemsetAsync(m.mbuf, 0, MultiBuf::bytes, s));
@@ -4064,32 +4118,21 @@ int sbp_multi_run(const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs, co
         HIPCHK(hipMemsetAsync(m.mbuf + MultiBuf::counters, 0, MultiBuf::counters_bytes, s));
         m.mdirty = false;
     }
-    unsigned long long* stats = t_stats ? ms_ptr<unsigned long long>(o_stats) : nullptr;
-    t_last_stats[0] = t_last_stats[1] = t_last_stats[2] = -1;
-    if (stats) HIPCHK(hipMemsetAsync(stats, 0, 24, s));
+    StatsScope stats;
+    MSCHK(stats.begin(o_stats, s));
     MsTimer timer(s);
     const FrameDev fr = fp.view();
     const uint8_t* q = dev ? (const uint8_t*)(fin ? (const void*)fin->pts : queries) : ms_ptr<const uint8_t>(o_q);
     int* ntm = fin ? ms_ptr<int>(o_ntm) : nullptr;
-    if (fin) {   // Tracking::SearchLocalPoints' isInFrustum, then the search
-        CamDev cd;
-        if (!make_camdev(F, fin->cam, fin->rig, cd)) return ORBFE_E_ARG;
-        HIPCHK(hipMemsetAsync(ntm, 0, 4, s));
-        hipLaunchKernelGGL(k_frustum, dim3((nq + MT_NT - 1) / MT_NT), dim3(MT_NT), 0, s, cd,
-                           (const orbfe_map_point_3d*)q, nq, ms_ptr<orbfe_map_point>(o_track), ntm, fin->track_dev);
-        t_ms.last_track = ms_ptr<const orbfe_map_point>(o_track);
-        t_ms.last_track_n = nq;
-        q = ms_ptr<const uint8_t>(o_track);
-        qstride = sizeof(orbfe_map_point);
-        qid_off = offsetof(orbfe_map_point, id);
-    }
+    // Tracking::SearchLocalPoints' isInFrustum, then the search
+    if (fin) MSCHK(frustum_stage(F, *fin, q, nq, o_track, ntm, s, q, rl));
     uint8_t* mb = m.mbuf;
     MultiIO io;
     io.mvp_in = dev ? mvp : ms_ptr<const int32_t>(o_mvp);
     io.obs_in = dev ? mvp_obs : ms_ptr<const int32_t>(o_obs);
     io.mvp_out = dev ? mvp : ms_ptr<int32_t>(o_mvp);
-    io.q_stride = (int)qstride;
-    io.qid_off = (int)qid_off;
+    io.q_stride = rl.stride;
+    io.qid_off = rl.id_off;
     io.ntm = ntm;
     io.assign = ms_ptr<int>(o_assign);
     io.lists = ms_ptr<uint32_t>(o_lists);
@@ -4107,7 +4150,7 @@ int sbp_multi_run(const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs, co
     io.g_be = ms_ptr<int>(o_gbe);
     io.g_blk = ms_ptr<uint8_t>(o_gblk);
     io.st_host = m.hs_dev;
-    io.stats = stats;
+    io.stats = stats.words;
     io.gen0 = m.gen;
     m.gen += MT_MAX_PASSES;
     const orbfe_map_point* recs = (const orbfe_map_point*)q;
@@ -4137,24 +4180,11 @@ int sbp_multi_run(const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs, co
                                    nnratio, pass, final_, io);
         }
         HIPCHK(hipGetLastError());
-        if (dev) {
-            HIPCHK(hipEventRecord(m.tail, s));
-            m.tail_stream = s;
-        }
+        MSCHK(ms_record_tail(dev, s));
         timer.end();
-        for (unsigned spin = 1; host_seq_acquire(st) != io.seq; spin++) {
-            if ((spin & 1023) == 0) {   // bounded: a stream that finished without publishing is an error
-                const hipError_t e = hipStreamQuery(s);
-                if (e == hipSuccess && host_seq_acquire(st) != io.seq) {
-                    m.mdirty = true;
-                    return ORBFE_E_DEVICE;
-                }
-                if (e != hipSuccess && e != hipErrorNotReady) {
-                    m.mdirty = true;
-                    HIPCHK(e);
-                }
-            }
-            __builtin_ia32_pause();
+        if (const int wrc = ms_wait_seq(s, io.seq)) {   // the unfinished call's counters may stay set
+            m.mdirty = true;
+            return wrc;
         }
         if (st[0] == 0) break;
         batch = 6;
@@ -4165,14 +4195,8 @@ int sbp_multi_run(const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs, co
         HIPCHK(hipStreamSynchronize(s));
     }
     if (fin && fin->n_to_match) *fin->n_to_match = st[5];
-    if (stats) {   // counting mode only: one more copy and synchronisation
-        unsigned long long hst[3];
-        HIPCHK(hipMemcpyAsync(hst, stats, 24, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        t_last_stats[0] = (long long)hst[1];
-        t_last_stats[1] = (long long)hst[1];
-        t_last_stats[2] = (long long)hst[2];
-    }
+    // multi_pass_end counts pairs only (word 1): they are reported as the window candidates as well
+    MSCHK(stats.read(s, 1));
     return st[1];
 }
 
@@ -4198,9 +4222,10 @@ int last_proj_host(const LastProjIn& lp, int nq, std::vector<orbfe_proj_point>& 
 }
 
 int sbp_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs, const void* queries, int nq,
-            size_t qstride, size_t qobs_off, size_t qid_off, size_t qangle_off, size_t qlevel_off, float th, int a0, int a1, float thFar,
-            float nnratio, int maxDist, int checkOri, const FrustumIn* fin = nullptr, const DevIn* dev = nullptr,
-            const float* right_uv = nullptr, const LastProjIn* lp = nullptr) {
+            const RecLayout& layout, float th, int a0, int a1, float thFar, float nnratio, int maxDist, int checkOri,
+            const FrustumIn* fin = nullptr, const DevIn* dev = nullptr, const float* right_uv = nullptr,
+            const LastProjIn* lp = nullptr) {
+    RecLayout rl = layout;
     // a device view of the current frame (orbfe_frame_device_view): the frame's arrays are read in HBM
     // by k_sbp_block; any other path would read them on the host, so other shapes are refused
     const bool fdev = F && F->device != 0;
@@ -4229,10 +4254,10 @@ int sbp_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs
     // (frustum-produced levels are clamped to [0, nlevels) by PredictScale; device-resident
     // records are not visible to the host: the kernels skip out-of-range levels instead)
     for (int j = 0; !fin && !dev && !lp && j < nq; j++) {
-        const uint8_t* rec = (const uint8_t*)queries + (size_t)j * qstride;
+        const uint8_t* rec = (const uint8_t*)queries + (size_t)j * rl.stride;
         const bool used = mode == 0 ? (((const orbfe_map_point*)rec)->flags & ORBFE_MP_IN_VIEW) != 0
                                     : ((const orbfe_proj_point*)rec)->valid != 0;
-        const int lvl = *(const int32_t*)(rec + qlevel_off);
+        const int lvl = *(const int32_t*)(rec + rl.level_off);
         if (used && (lvl < 0 || lvl >= F->nlevels)) return ORBFE_E_ARG;
         if (two && mode == 0) {
             const orbfe_map_point* m = (const orbfe_map_point*)rec;
@@ -4251,18 +4276,18 @@ int sbp_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs
     BlkGeom gm;
     if (W == 1 && n <= MT_BAND_MAXN && blk_geom(F, gm)) {
         if (nq <= MT_BLOCK_MAXQ)
-            return sbp_block_run(mode, F, mvp, mvp_obs, queries, nq, qstride, qid_off, qangle_off, th, a0, a1, thFar,
-                                 nnratio, maxDist, checkOri, gm, fin, dev, lp);
+            return sbp_block_run(mode, F, mvp, mvp_obs, queries, nq, rl, th, a0, a1, thFar, nnratio, maxDist, checkOri,
+                                 gm, fin, dev, lp);
         // narrow windows only: a wide window is a long serial walk for one thread, where k_sbp_band's
         // sixteen lanes per query win (config 5: th 1 / 3 here, th 5 / 15 there; r05_kernel_ab.txt)
         if (mode == 0 && th < MT_MULTI_TH)
-            return sbp_multi_run(F, mvp, mvp_obs, queries, nq, qstride, qid_off, th, a0, thFar, nnratio, gm, fin, dev);
+            return sbp_multi_run(F, mvp, mvp_obs, queries, nq, rl, th, a0, thFar, nnratio, gm, fin, dev);
     }
     // a two-camera frame's local-map search (SearchLocalPoints of a KannalaBrandt8 rig) in one
     // workgroup: four slot writes per point, the slots' writers tracked per pass (k_sbp_block4)
     if (two && mode == 0 && n <= MT_BAND_MAXN && nq <= MT_BLOCK_MAXQ && blk_geom(F, gm, 2, blk4_bytes_per_kp())) {
-        const int r = sbp_block_run(0, F, mvp, mvp_obs, queries, nq, qstride, qid_off, qangle_off, th, a0, a1, thFar,
-                                    nnratio, maxDist, 0, gm, fin, dev);
+        const int r = sbp_block_run(0, F, mvp, mvp_obs, queries, nq, rl, th, a0, a1, thFar, nnratio, maxDist, 0, gm,
+                                    fin, dev);
         if (r != kBlockAborted) return r;
     }
     // a two-camera frame's last-frame search (the per-frame Tracking call of a KannalaBrandt8 rig) in
@@ -4287,7 +4312,7 @@ int sbp_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs
     if (dev) fp.plan_dev(F, mode != 2);
     else fp.plan(p, F, true, mode != 2);
     const size_t o_q = dev ? 0 : fin ? p.upload(fin->pts, (size_t)nq * sizeof(orbfe_map_point_3d))
-                                     : p.upload(queries, (size_t)nq * qstride);
+                                     : p.upload(queries, (size_t)nq * rl.stride);
     const size_t o_b0 = dev ? 0 : p.upload(blocked0.data(), (size_t)n * 4);
     const size_t o_mvp = dev ? 0 : p.upload(mvp, (size_t)n * 4);
     const size_t o_b0d = dev ? p.scratch((size_t)n * 4) : 0;
@@ -4315,17 +4340,15 @@ int sbp_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs
     const size_t o_changed = p.scratch(MT_MAX_PASSES * 4);
     const size_t o_result = p.scratch((size_t)(n + 3) * 4);   // [change flag copy | counts | slots]
     const size_t o_hist = p.scratch((MT_HISTO + 1) * 4);   // rotation bins + commit completion counter
-    const size_t o_stats = t_stats ? p.scratch(24) : 0;
-    int rc = ms_prepare(p);
-    if (rc) return rc;
+    const size_t o_stats = stats_plan(p);
+    MSCHK(ms_prepare(p));
     // a device-resident search runs on the caller's stream, after the producer of its inputs; it
     // returns once its status is published and records MatchScratch::tail, after which the next
     // call of the thread orders itself (host-API calls also end with a stream synchronisation)
-    hipStream_t s = dev ? dev->caller : t_ms.stream;
-    if (dev) HIPCHK(ms_after_tail(s));
-    unsigned long long* stats = t_stats ? ms_ptr<unsigned long long>(o_stats) : nullptr;
-    t_last_stats[0] = t_last_stats[1] = t_last_stats[2] = -1;
-    if (stats) HIPCHK(hipMemsetAsync(stats, 0, 24, s));
+    hipStream_t s;
+    MSCHK(ms_call_stream(dev, s));
+    StatsScope stats;
+    MSCHK(stats.begin(o_stats, s));
     MsTimer timer(s);
     const FrameDev fr = fp.view();
     const int* b0 = dev ? ms_ptr<const int>(o_b0d) : ms_ptr<const int>(o_b0);
@@ -4343,21 +4366,12 @@ int sbp_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs
     const float2* ruv = (two && mode == 1) ? (dev ? (const float2*)right_uv : ms_ptr<const float2>(o_ruv)) : nullptr;
     const uint8_t* q = dev ? (const uint8_t*)(fin ? (const void*)fin->pts : queries) : ms_ptr<const uint8_t>(o_q);
     if (fin) {   // Tracking::SearchLocalPoints: project, count nToMatch, match only if > 0
-        CamDev cd;
-        if (!make_camdev(F, fin->cam, fin->rig, cd)) return ORBFE_E_ARG;
         int* ntm = ms_ptr<int>(o_ntm);
-        HIPCHK(hipMemsetAsync(ntm, 0, 4, s));
-        hipLaunchKernelGGL(k_frustum, dim3((nq + MT_NT - 1) / MT_NT), dim3(MT_NT), 0, s, cd,
-                           (const orbfe_map_point_3d*)q, nq, ms_ptr<orbfe_map_point>(o_track), ntm, fin->track_dev);
-        t_ms.last_track = ms_ptr<const orbfe_map_point>(o_track);
-        t_ms.last_track_n = nq;
+        MSCHK(frustum_stage(F, *fin, q, nq, o_track, ntm, s, q, rl));
         int h_ntm = 0;
-        HIPCHK(hipMemcpyAsync(t_ms.hs, ntm, 4, hipMemcpyDeviceToHost, s));   // pinned
-        HIPCHK(hipStreamSynchronize(s));
-        h_ntm = t_ms.hs[0];
+        MSCHK(ms_read_int(ntm, s, h_ntm));
         if (fin->n_to_match) *fin->n_to_match = h_ntm;
         if (h_ntm <= 0) return 0;
-        q = ms_ptr<const uint8_t>(o_track);
     }
     const dim3 gq((nq + MT_NT - 1) / MT_NT);
     const bool staged = n <= MT_STAGE_MAX;
@@ -4366,13 +4380,13 @@ int sbp_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs
     // the commit runs once (a gated commit that does not run leaves result / hist as the
     // initialisation set them); st_host: where the last kernel stores the status the host reads
     auto commit = [&](const int* gate, const CommitStatus& cs) {
-        hipLaunchKernelGGL(k_mt_commit_count, ge, dim3(MT_NT), 0, s, fr.keys, assign, (const float*)(q + qangle_off),
-                           (int)qstride, nq * W, checkOri, result, hist, W, gate);
+        hipLaunchKernelGGL(k_mt_commit_count, ge, dim3(MT_NT), 0, s, fr.keys, assign, (const float*)(q + rl.angle_off),
+                           rl.stride, nq * W, checkOri, result, hist, W, gate);
         if (checkOri)
             hipLaunchKernelGGL(k_mt_commit_drop, ge, dim3(MT_NT), 0, s, fr.keys, assign,
-                               (const float*)(q + qangle_off), (int)qstride, nq * W, hist, result, W, gate);
-        hipLaunchKernelGGL(k_mt_commit_write, dim3((n + 255) / 256), dim3(256), 0, s, n, (const int*)(q + qid_off),
-                           (int)qstride, result, mvp_d, W, gate, resb, cs);
+                               (const float*)(q + rl.angle_off), rl.stride, nq * W, hist, result, W, gate);
+        hipLaunchKernelGGL(k_mt_commit_write, dim3((n + 255) / 256), dim3(256), 0, s, n, (const int*)(q + rl.id_off),
+                           rl.stride, result, mvp_d, W, gate, resb, cs);
         return ORBFE_OK;
     };
     int pass = 0;
@@ -4390,7 +4404,7 @@ int sbp_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs
             for (int c = 0; c < batch; c++, pass++) {
                 if (pass >= MT_MAX_PASSES) return ORBFE_E_CAPACITY;
                 PassIO io{pass ? changed + pass - 1 : nullptr, fb[(pass + 1) % 4], fb[(pass + 2) % 4], n,
-                          mode == 2 ? 0 : 1, stats};
+                          mode == 2 ? 0 : 1, stats.words};
                 const int* fcur = fb[pass % 4];
                 // pass 1 sees nearly every gate move (free -> first claimer): skipping from pass 2 on
                 const int* fprev = pass >= 2 ? fb[(pass + 3) % 4] : nullptr;
@@ -4438,33 +4452,16 @@ int sbp_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs
             const int seq = ++t_ms.seq;
             commit(changed + pass - 1, CommitStatus{t_ms.hs_dev, hist + MT_HISTO, changed + pass0, batch, seq});
             HIPCHK(hipGetLastError());
-            if (dev) {
-                HIPCHK(hipEventRecord(t_ms.tail, s));
-                t_ms.tail_stream = s;
-            }
+            MSCHK(ms_record_tail(dev, s));
             timer.end();
             if (!dev) {
                 HIPCHK(hipMemcpyAsync(mvp, mvp_d, (size_t)n * 4, hipMemcpyDeviceToHost, s));
                 HIPCHK(hipStreamSynchronize(s));
             }
-            for (unsigned spin = 1; host_seq_acquire(st) != seq; spin++) {
-                if ((spin & 1023) == 0) {   // bounded: a stream that finished without publishing is an error
-                    const hipError_t e = hipStreamQuery(s);
-                    if (e == hipSuccess && host_seq_acquire(st) != seq) return ORBFE_E_DEVICE;
-                    if (e != hipSuccess && e != hipErrorNotReady) HIPCHK(e);
-                }
-                __builtin_ia32_pause();
-            }
+            MSCHK(ms_wait_seq(s, seq));
             if (st[0] == 0) {
                 t_ms.pass_hint[mode] = pass0 + st[3];
-                if (stats) {   // counting mode only: one more copy and synchronisation
-                    unsigned long long hst[3];
-                    HIPCHK(hipMemcpyAsync(hst, stats, 24, hipMemcpyDeviceToHost, s));
-                    HIPCHK(hipStreamSynchronize(s));
-                    t_last_stats[0] = (long long)hst[0];
-                    t_last_stats[1] = (long long)hst[1];
-                    t_last_stats[2] = pass0 + st[3];
-                }
+                MSCHK(stats.read(s, 0, pass0 + st[3]));   // the passes of every round trip, not the last one's
                 return st[1] - st[2];
             }
             batch = 6;
@@ -4489,15 +4486,14 @@ int sbp_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs
                 continue;
             }
             fill(first, n, MT_INF, s);
-            hipLaunchKernelGGL(k_mt_first_strided, gw, dim3(MT_NT), 0, s, assign, q + qobs_off, (int)qstride, nq * W,
+            hipLaunchKernelGGL(k_mt_first_strided, gw, dim3(MT_NT), 0, s, assign, q + rl.obs_off, rl.stride, nq * W,
                                mode == 2 ? 0 : 1, first, W);
             hipLaunchKernelGGL(k_sbp_proj2, gq, dim3(MT_NT), 0, s, fr, (const orbfe_proj_point*)q, ruv, nq, th, a0,
                                a1, b0, first, assign, changed + pass);
         }
-        int* ch = t_ms.hs;   // pinned: a pageable 4-byte read back costs more than the passes
-        HIPCHK(hipMemcpyAsync(ch, changed + pass - 1, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (*ch == 0) break;
+        int ch = 0;
+        MSCHK(ms_read_int(changed + pass - 1, s, ch));
+        if (ch == 0) break;
     }
     commit(nullptr, CommitStatus{});
     HIPCHK(hipGetLastError());
@@ -4529,16 +4525,14 @@ extern "C" {
 int orbfe_search_by_projection_local(const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs,
                                      const orbfe_map_point* mps, int32_t n_mps, float th, int32_t bFarPoints,
                                      float thFarPoints, float nnratio) {
-    return sbp_run(0, F, mvp, mvp_obs, mps, n_mps, sizeof(orbfe_map_point), offsetof(orbfe_map_point, observations),
-                   offsetof(orbfe_map_point, id), 0, offsetof(orbfe_map_point, scale_level), th, bFarPoints, 0, thFarPoints, nnratio, 0, 0);
+    return sbp_run(0, F, mvp, mvp_obs, mps, n_mps, kMapPointRec, th, bFarPoints, 0, thFarPoints, nnratio, 0, 0);
 }
 
 int orbfe_search_by_projection_lastframe_stereo(const orbfe_frame* cur, int32_t* mvp, const int32_t* mvp_obs,
                                                 const orbfe_proj_point* pts, const float* right_uv, int32_t n_pts,
                                                 float th, int32_t bForward, int32_t bBackward, int32_t checkOri) {
-    return sbp_run(1, cur, mvp, mvp_obs, pts, n_pts, sizeof(orbfe_proj_point), offsetof(orbfe_proj_point, observations),
-                   offsetof(orbfe_proj_point, id), offsetof(orbfe_proj_point, angle), offsetof(orbfe_proj_point, octave),
-                   th, bForward, bBackward, 0.f, 0.f, MT_TH_HIGH, checkOri, nullptr, nullptr, right_uv);
+    return sbp_run(1, cur, mvp, mvp_obs, pts, n_pts, kProjPointRec, th, bForward, bBackward, 0.f, 0.f, MT_TH_HIGH,
+                   checkOri, nullptr, nullptr, right_uv);
 }
 
 int orbfe_search_by_projection_lastframe_pose(const orbfe_frame* cur, int32_t* mvp, const int32_t* mvp_obs,
@@ -4565,25 +4559,20 @@ int orbfe_search_by_projection_lastframe_pose(const orbfe_frame* cur, int32_t* m
     lp.cam.type = cam->type;
     lp.cam.fx = cam->params[0]; lp.cam.fy = cam->params[1]; lp.cam.cx = cam->params[2]; lp.cam.cy = cam->params[3];
     for (int k = 0; k < 4; k++) lp.cam.k[k] = cam->type == ORBFE_CAM_KANNALA_BRANDT8 ? cam->params[4 + k] : 0.f;
-    return sbp_run(1, cur, mvp, mvp_obs, nullptr, n_pts, sizeof(orbfe_proj_point),
-                   offsetof(orbfe_proj_point, observations), offsetof(orbfe_proj_point, id),
-                   offsetof(orbfe_proj_point, angle), offsetof(orbfe_proj_point, octave), th, bForward, bBackward, 0.f, 0.f,
-                   MT_TH_HIGH, checkOri, nullptr, nullptr, nullptr, &lp);
+    return sbp_run(1, cur, mvp, mvp_obs, nullptr, n_pts, kProjPointRec, th, bForward, bBackward, 0.f, 0.f, MT_TH_HIGH,
+                   checkOri, nullptr, nullptr, nullptr, &lp);
 }
 
 int orbfe_search_by_projection_lastframe(const orbfe_frame* cur, int32_t* mvp, const int32_t* mvp_obs,
                                          const orbfe_proj_point* pts, int32_t n_pts, float th, int32_t bForward,
                                          int32_t bBackward, int32_t checkOri) {
-    return sbp_run(1, cur, mvp, mvp_obs, pts, n_pts, sizeof(orbfe_proj_point),
-                   offsetof(orbfe_proj_point, observations), offsetof(orbfe_proj_point, id),
-                   offsetof(orbfe_proj_point, angle), offsetof(orbfe_proj_point, octave), th, bForward, bBackward, 0.f, 0.f, MT_TH_HIGH, checkOri);
+    return sbp_run(1, cur, mvp, mvp_obs, pts, n_pts, kProjPointRec, th, bForward, bBackward, 0.f, 0.f, MT_TH_HIGH,
+                   checkOri);
 }
 
 int orbfe_search_by_projection_kf(const orbfe_frame* cur, int32_t* mvp, const orbfe_proj_point* pts, int32_t n_pts,
                                   float th, int32_t ORBdist, int32_t checkOri) {
-    return sbp_run(2, cur, mvp, nullptr, pts, n_pts, sizeof(orbfe_proj_point),
-                   offsetof(orbfe_proj_point, observations), offsetof(orbfe_proj_point, id),
-                   offsetof(orbfe_proj_point, angle), offsetof(orbfe_proj_point, octave), th, 0, 0, 0.f, 0.f, ORBdist, checkOri);
+    return sbp_run(2, cur, mvp, nullptr, pts, n_pts, kProjPointRec, th, 0, 0, 0.f, 0.f, ORBdist, checkOri);
 }
 
 static int sfi_core(const orbfe_frame* F1, const orbfe_frame* F2, float* prev_matched, int32_t* matches12,
@@ -4674,16 +4663,8 @@ static int sfi_core(const orbfe_frame* F1, const orbfe_frame* F2, float* prev_ma
     fill(adist, n1, 0);
     const dim3 gq((n1 + MT_INIT_WNT / 16 - 1) / (MT_INIT_WNT / 16));   // four queries per wave
     // outputs in mapped pinned memory: matches12, then prevMatched (the input, updated by the commit)
+    MSCHK(ms_out_block((size_t)n1 * 3, std::max<size_t>((size_t)n1 * 3, 2048)));
     MatchScratch& m = t_ms;
-    if (m.ocap < (size_t)n1 * 3) {
-        if (m.ho) HIPCHK(hipHostFree(m.ho));
-        m.ho = nullptr;
-        m.ocap = 0;
-        const size_t cap = std::max<size_t>((size_t)n1 * 3, 2048);
-        HIPCHK(hipHostMalloc((void**)&m.ho, cap * 4, hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostGetDevicePointer((void**)&m.ho_dev, m.ho, 0));
-        m.ocap = cap;
-    }
     memcpy(m.ho + n1, prev_matched, (size_t)n1 * 8);
     // gated passes (a pass after an unchanged one returns at once) and a gated commit per round trip:
     // the host waits for the commit's status words, and enqueues more passes only when the last one
@@ -4706,15 +4687,8 @@ static int sfi_core(const orbfe_frame* F1, const orbfe_frame* F2, float* prev_ma
                            (float*)(m.ho_dev + n1), m.ho_dev, changed + pass - 1, t_ms.hs_dev, seq);
         HIPCHK(hipGetLastError());
         timer.end();
+        MSCHK(ms_wait_seq(s, seq));
         volatile int* st = t_ms.hs;
-        for (unsigned spin = 1; host_seq_acquire(st) != seq; spin++) {
-            if ((spin & 1023) == 0) {   // bounded: a stream that finished without publishing is an error
-                const hipError_t e = hipStreamQuery(s);
-                if (e == hipSuccess && host_seq_acquire(st) != seq) return ORBFE_E_DEVICE;
-                if (e != hipSuccess && e != hipErrorNotReady) HIPCHK(e);
-            }
-            __builtin_ia32_pause();
-        }
         if (st[0] == 0) {   // converged and committed: the outputs precede the status words
             memcpy(matches12, m.ho, (size_t)n1 * 4);
             memcpy(prev_matched, m.ho + n1, (size_t)n1 * 8);
@@ -4787,16 +4761,8 @@ int orbfe_search_by_bow(const orbfe_keypoint* kf_keys, const uint8_t* kf_desc, c
     MsTimer timer;
     hipStream_t s = t_ms.stream;
     if (block) {
+        MSCHK(ms_out_block((size_t)fn, std::max<size_t>((size_t)fn, 2048)));
         MatchScratch& m = t_ms;
-        if (m.ocap < (size_t)fn) {
-            if (m.ho) HIPCHK(hipHostFree(m.ho));
-            m.ho = nullptr;
-            m.ocap = 0;
-            const size_t cap = std::max<size_t>((size_t)fn, 2048);
-            HIPCHK(hipHostMalloc((void**)&m.ho, cap * 4, hipHostMallocMapped | hipHostMallocCoherent));
-            HIPCHK(hipHostGetDevicePointer((void**)&m.ho_dev, m.ho, 0));
-            m.ocap = cap;
-        }
         auto rel = [&](size_t o) { return (int)(o - o_pairs); };
         const int seq = ++t_ms.seq;
         BowBlockIn in{up_ptr<const uint4>(o_pairs, true), (int)((reg_bytes + 15) / 16), rel(o_pairs), rel(o_kfoff),
@@ -4806,15 +4772,8 @@ int orbfe_search_by_bow(const orbfe_keypoint* kf_keys, const uint8_t* kf_desc, c
         hipLaunchKernelGGL(k_bow_block, dim3(1), dim3(MT_BOW_NT), blds, s, in, m.ho_dev, ms_ptr<int>(o_result));
         HIPCHK(hipGetLastError());
         timer.end();
+        MSCHK(ms_wait_seq(s, seq));
         volatile int* st = t_ms.hs;
-        for (unsigned spin = 1; host_seq_acquire(st) != seq; spin++) {
-            if ((spin & 1023) == 0) {   // bounded: a stream that finished without publishing is an error
-                const hipError_t e = hipStreamQuery(s);
-                if (e == hipSuccess && host_seq_acquire(st) != seq) return ORBFE_E_DEVICE;
-                if (e != hipSuccess && e != hipErrorNotReady) HIPCHK(e);
-            }
-            __builtin_ia32_pause();
-        }
         memcpy(out, m.ho, (size_t)fn * 4);   // complete: the status words come after the output stores
         return st[1];
     }
@@ -4830,9 +4789,7 @@ int orbfe_search_by_bow(const orbfe_keypoint* kf_keys, const uint8_t* kf_desc, c
     timer.end();
     int nm = 0;
     HIPCHK(hipMemcpyAsync(out, ms_ptr<int>(o_out), (size_t)fn * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(t_ms.hs, ms_ptr<int>(o_result), 4, hipMemcpyDeviceToHost, s));   // pinned
-    HIPCHK(hipStreamSynchronize(s));
-    nm = t_ms.hs[0];
+    MSCHK(ms_read_int(ms_ptr<int>(o_result), s, nm));
     return nm;
 }
 
@@ -4994,17 +4951,9 @@ int orbfe_search_by_bow_batch(const orbfe_keyframe* const* kfs, const int32_t* c
         if (cands[c].mode == 2) o_src[c] = p.scratch((size_t)fn * 4);
     int rc = ms_prepare(p);
     if (rc) return rc;
-    MatchScratch& m = t_ms;
     const size_t nout = (size_t)n_kfs * fn + (size_t)n_kfs;   // the rows, then nmatches
-    if (m.ocap < nout) {
-        if (m.ho) HIPCHK(hipHostFree(m.ho));
-        m.ho = nullptr;
-        m.ocap = 0;
-        const size_t cap = std::max<size_t>(nout + nout / 2, 2048);
-        HIPCHK(hipHostMalloc((void**)&m.ho, cap * 4, hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostGetDevicePointer((void**)&m.ho_dev, m.ho, 0));
-        m.ocap = cap;
-    }
+    MSCHK(ms_out_block(nout, std::max<size_t>(nout + nout / 2, 2048)));
+    MatchScratch& m = t_ms;
     MsTimer timer;
     hipStream_t s = m.stream;
     int* d_out = m.ho_dev;
@@ -5136,18 +5085,15 @@ int orbfe_search_local_points(const orbfe_frame* F, const orbfe_camera* cam, con
     if (F && F->n == 0 && n > 0 && pts && cam && !F->two_cams)
         return empty_frame_n_to_match(F, cam, nullptr, pts, n, n_to_match);
     const FrustumIn fin{cam, pts, n_to_match, nullptr};
-    return sbp_run(0, F, mvp, mvp_obs, nullptr, n, sizeof(orbfe_map_point), offsetof(orbfe_map_point, observations),
-                   offsetof(orbfe_map_point, id), 0, offsetof(orbfe_map_point, scale_level), th, bFarPoints, 0,
-                   thFarPoints, nnratio, 0, 0, &fin);
+    return sbp_run(0, F, mvp, mvp_obs, nullptr, n, kMapPointRec, th, bFarPoints, 0, thFarPoints, nnratio, 0, 0, &fin);
 }
 
 int orbfe_search_by_projection_local_device(const orbfe_frame* F, int32_t* d_mvp, const int32_t* d_mvp_obs,
                                             const orbfe_map_point* d_mps, int32_t n_mps, float th,
                                             int32_t bFarPoints, float thFarPoints, float nnratio, void* stream) {
     const DevIn dv{(hipStream_t)stream};
-    return sbp_run(0, F, d_mvp, d_mvp_obs, d_mps, n_mps, sizeof(orbfe_map_point), offsetof(orbfe_map_point, observations),
-                   offsetof(orbfe_map_point, id), 0, offsetof(orbfe_map_point, scale_level), th, bFarPoints, 0,
-                   thFarPoints, nnratio, 0, 0, nullptr, &dv);
+    return sbp_run(0, F, d_mvp, d_mvp_obs, d_mps, n_mps, kMapPointRec, th, bFarPoints, 0, thFarPoints, nnratio, 0, 0,
+                   nullptr, &dv);
 }
 
 int orbfe_search_local_points_device(const orbfe_frame* F, const orbfe_camera* cam, const orbfe_map_point_3d* d_pts,
@@ -5156,9 +5102,8 @@ int orbfe_search_local_points_device(const orbfe_frame* F, const orbfe_camera* c
                                      void* stream) {
     const FrustumIn fin{cam, d_pts, n_to_match, nullptr};
     const DevIn dv{(hipStream_t)stream};
-    return sbp_run(0, F, d_mvp, d_mvp_obs, nullptr, n, sizeof(orbfe_map_point), offsetof(orbfe_map_point, observations),
-                   offsetof(orbfe_map_point, id), 0, offsetof(orbfe_map_point, scale_level), th, bFarPoints, 0,
-                   thFarPoints, nnratio, 0, 0, &fin, &dv);
+    return sbp_run(0, F, d_mvp, d_mvp_obs, nullptr, n, kMapPointRec, th, bFarPoints, 0, thFarPoints, nnratio, 0, 0,
+                   &fin, &dv);
 }
 
 int orbfe_search_local_points_rig(const orbfe_frame* F, const orbfe_camera* cam, const orbfe_stereo_rig* rig,
@@ -5167,9 +5112,7 @@ int orbfe_search_local_points_rig(const orbfe_frame* F, const orbfe_camera* cam,
     if (!rig) return ORBFE_E_ARG;
     if (F && F->n == 0 && n > 0 && pts && cam) return empty_frame_n_to_match(F, cam, rig, pts, n, n_to_match);
     const FrustumIn fin{cam, pts, n_to_match, rig};
-    return sbp_run(0, F, mvp, mvp_obs, nullptr, n, sizeof(orbfe_map_point), offsetof(orbfe_map_point, observations),
-                   offsetof(orbfe_map_point, id), 0, offsetof(orbfe_map_point, scale_level), th, bFarPoints, 0,
-                   thFarPoints, nnratio, 0, 0, &fin);
+    return sbp_run(0, F, mvp, mvp_obs, nullptr, n, kMapPointRec, th, bFarPoints, 0, thFarPoints, nnratio, 0, 0, &fin);
 }
 
 int orbfe_search_local_points_rig_device(const orbfe_frame* F, const orbfe_camera* cam, const orbfe_stereo_rig* rig,
@@ -5179,9 +5122,8 @@ int orbfe_search_local_points_rig_device(const orbfe_frame* F, const orbfe_camer
     if (!rig) return ORBFE_E_ARG;
     const FrustumIn fin{cam, d_pts, n_to_match, rig};
     const DevIn dv{(hipStream_t)stream};
-    return sbp_run(0, F, d_mvp, d_mvp_obs, nullptr, n, sizeof(orbfe_map_point), offsetof(orbfe_map_point, observations),
-                   offsetof(orbfe_map_point, id), 0, offsetof(orbfe_map_point, scale_level), th, bFarPoints, 0,
-                   thFarPoints, nnratio, 0, 0, &fin, &dv);
+    return sbp_run(0, F, d_mvp, d_mvp_obs, nullptr, n, kMapPointRec, th, bFarPoints, 0, thFarPoints, nnratio, 0, 0,
+                   &fin, &dv);
 }
 
 int orbfe_search_local_points_track(const orbfe_frame* F, const orbfe_camera* cam, const orbfe_stereo_rig* rig,
@@ -5221,9 +5163,8 @@ int orbfe_search_local_points_track(const orbfe_frame* F, const orbfe_camera* ca
     FrustumIn fin{cam, pts, n_to_match, rig};
     fin.track_dev = m.th_dev;
     const orbfe_map_point* th_host = m.th;
-    const int r = sbp_run(0, F, mvp, mvp_obs, nullptr, n, sizeof(orbfe_map_point), offsetof(orbfe_map_point, observations),
-                          offsetof(orbfe_map_point, id), 0, offsetof(orbfe_map_point, scale_level), th, bFarPoints, 0,
-                          thFarPoints, nnratio, 0, 0, &fin);
+    const int r = sbp_run(0, F, mvp, mvp_obs, nullptr, n, kMapPointRec, th, bFarPoints, 0, thFarPoints, nnratio, 0, 0,
+                          &fin);
     if (r < 0) return r;
     std::atomic_thread_fence(std::memory_order_acquire);
     memcpy(track, th_host, (size_t)n * sizeof(orbfe_map_point));
@@ -5248,20 +5189,16 @@ int orbfe_is_in_frustum_rig(const orbfe_frame* F, const orbfe_camera* cam, const
     if (rc) return rc;
     MsTimer timer;
     hipStream_t s = t_ms.stream;
-    CamDev cd;
-    if (!make_camdev(F, cam, rig, cd)) return ORBFE_E_ARG;
+    const FrustumIn fin{cam, pts, nullptr, rig};
     int* ntm = ms_ptr<int>(o_ntm);
-    HIPCHK(hipMemsetAsync(ntm, 0, 4, s));
-    hipLaunchKernelGGL(k_frustum, dim3((n + MT_NT - 1) / MT_NT), dim3(MT_NT), 0, s, cd,
-                       ms_ptr<const orbfe_map_point_3d>(o_pts), n, ms_ptr<orbfe_map_point>(o_track), ntm);
+    const uint8_t* recs = nullptr;
+    RecLayout rl;
+    MSCHK(frustum_stage(F, fin, ms_ptr<const void>(o_pts), n, o_track, ntm, s, recs, rl));
     HIPCHK(hipGetLastError());
     timer.end();
     int h_ntm = 0;
-    HIPCHK(hipMemcpyAsync(track, ms_ptr<orbfe_map_point>(o_track), (size_t)n * sizeof(orbfe_map_point),
-                          hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(t_ms.hs, ntm, 4, hipMemcpyDeviceToHost, s));   // pinned
-    HIPCHK(hipStreamSynchronize(s));
-    h_ntm = t_ms.hs[0];
+    HIPCHK(hipMemcpyAsync(track, recs, (size_t)n * sizeof(orbfe_map_point), hipMemcpyDeviceToHost, s));
+    MSCHK(ms_read_int(ntm, s, h_ntm));
     return h_ntm;
 }
 
