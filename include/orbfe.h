@@ -755,6 +755,68 @@ int orbfe_vocabulary_transform(const orbfe_vocabulary* voc, const uint8_t* desc,
                                uint32_t* fv_node_ids, int32_t* fv_offsets, uint32_t* fv_indices, int32_t* fv_n);
 
 /* ---------------------------------------------------------------------------------------------
+ * KeyFrameDatabase for relocalisation (KeyFrameDatabase.cc:39-77, :733-845): the one method of the
+ * keyframe database that Tracking calls, Tracking::Relocalization's DetectRelocalizationCandidates.
+ * Every added keyframe's mBowVec is kept in HBM; a query uploads only the frame's BowVector.
+ * Keyframes are named by caller-chosen ids >= 0 (an index into the caller's own KeyFrame* table).
+ * Only L1 scoring is supported (L1Scoring::score, ScoringObject.cpp:23-68: ORBVocabulary is L1 /
+ * TF-IDF); weights are stored as given and never normalised.
+ *
+ * One mutex inside the handle serialises every call (KeyFrameDatabase::mMutex): add / erase may come
+ * from LocalMapping while Tracking queries. The handle belongs to the HIP device current at create;
+ * a call that needs the device with another one current returns ORBFE_E_ARG. Created with no device
+ * visible, the handle still answers everything that needs none (argument checks, empty BowVectors,
+ * empty queries) and returns ORBFE_E_DEVICE otherwise. Results are complete on return.
+ *
+ * ORBFE_E_ARG, before any device call: a NULL handle or NULL output, n_words <= 0, n < 0, cap < 0,
+ * kf_id < 0, word ids that do not strictly ascend or reach n_words (add and queries), a kf_id that
+ * is already present (add) or absent (erase).
+ *
+ * Departure from the reference: the per-keyframe query state (mRelocScore) belongs to the database
+ * entry, so erase drops it and a later add of the same id starts from 0 again. In the reference a
+ * keyframe is erased only when it goes bad and is never added again.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct orbfe_kfdb orbfe_kfdb;
+int orbfe_kfdb_create(int32_t n_words, orbfe_kfdb** out);   /* mvInvertedFile.resize(mpVoc->size()) */
+void orbfe_kfdb_destroy(orbfe_kfdb* db);                    /* NULL is a no-op; must not race a call on db */
+/* KeyFrameDatabase::add: word_ids ascending (a BowVector is a std::map), n == 0 is legal (the keyframe
+ * can never share a word). The keyframe goes to the back of every word's list: entries are ordered
+ * by their add, so erase followed by add moves a keyframe to the back. The arrays are free on return. */
+int orbfe_kfdb_add(orbfe_kfdb* db, int32_t kf_id, const uint32_t* word_ids, const double* weights, int32_t n);
+int orbfe_kfdb_erase(orbfe_kfdb* db, int32_t kf_id);        /* KeyFrameDatabase::erase */
+int orbfe_kfdb_clear(orbfe_kfdb* db);                       /* KeyFrameDatabase::clear */
+int orbfe_kfdb_size(const orbfe_kfdb* db);                  /* keyframes present */
+
+/* Stages 1 and 2 of DetectRelocalizationCandidates (:735-787). Outputs, *n_out entries of capacity
+ * cap: lKFsSharingWords in the reference's list order (F's words ascending, each word's list in add
+ * order) as kf_ids, their mnRelocWords as words, and for the entries with
+ * words > int(maxCommonWords * 0.8f) scored = 1 and scores = float(L1Scoring::score(F, KF)) (else
+ * 0 and 0.f). The score's double sum runs over the shared words in ascending word id as one
+ * left-to-right chain, as the reference's. *max_common_words = maxCommonWords (0 for an empty list).
+ * A scored keyframe's mRelocScore is updated, as the reference updates it. cap smaller than the list:
+ * ORBFE_E_ARG with *n_out = the needed count, nothing else written and no state changed.
+ * f_n == 0 or an empty database: ORBFE_OK with *n_out = 0. */
+int orbfe_kfdb_shared_words(orbfe_kfdb* db, const uint32_t* f_word_ids, const double* f_weights, int32_t f_n,
+                            int32_t* kf_ids, int32_t* words, float* scores, uint8_t* scored, int32_t cap,
+                            int32_t* n_out, int32_t* max_common_words);
+
+/* Per keyframe: GetBestCovisibilityKeyFrames(10) as ids into neighbours10 (returns their count, 0..10;
+ * anything else makes the query return ORBFE_E_ARG) and GetMap() as an id into *map_id. Called on the
+ * calling thread while the handle's mutex is held (it must not call into the same handle), at most
+ * once per keyframe id and query. */
+typedef int32_t (*orbfe_kf_info_fn)(void* ctx, int32_t kf_id, int32_t* neighbours10, int32_t* map_id);
+
+/* The whole method (:733-845): vpRelocCandidates as keyframe ids in the reference's order. The
+ * covisibility pass reads mRelocScore of every neighbour that shares a word with F in this query,
+ * scored in this query or not (a stale score from an earlier query counts, as in the reference);
+ * neighbour ids that are not in the database or share no word are skipped. info == NULL: no keyframe
+ * has neighbours and every keyframe is in map_id. The tail (:792-844) runs on the host in float.
+ * cap smaller than the result: ORBFE_E_ARG with *n_out = the needed count, no state changed. */
+int orbfe_kfdb_detect_reloc(orbfe_kfdb* db, const uint32_t* f_word_ids, const double* f_weights, int32_t f_n,
+                            int32_t map_id, orbfe_kf_info_fn info, void* ctx, int32_t* out_ids, int32_t cap,
+                            int32_t* n_out);
+
+/* ---------------------------------------------------------------------------------------------
  * Stereo rectification: cv::remap(im, out, M1, M2, cv::INTER_LINEAR) with CV_32F
  * maps from initUndistortRectifyMap (System.cc:233-240, Settings.cc:506-509), BORDER_CONSTANT 0.
  * ------------------------------------------------------------------------------------------- */

@@ -23,6 +23,9 @@ STAGE_NAMES = ("pyramid_fast", "octree", "describe")
 
 # orbfe_epipolar_fn: int32_t (*)(void* ctx, int32_t idx1, int32_t idx2)
 EPIPOLAR_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32)
+# orbfe_kf_info_fn: int32_t (*)(void* ctx, int32_t kf_id, int32_t* neighbours10, int32_t* map_id)
+KF_INFO_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                              ctypes.POINTER(ctypes.c_int32))
 
 
 class OrbKeyPoint(ctypes.Structure):
@@ -137,6 +140,14 @@ _SIGS = {
     "orbfe_rgbd_stereo_batch": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp]),
     "orbfe_frame_rgbd": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int,
                                   _P_int, _vp, _vp]),
+    "orbfe_kfdb_create": (_c_int, [_c_int, ctypes.POINTER(_vp)]),
+    "orbfe_kfdb_destroy": (None, [_vp]),
+    "orbfe_kfdb_add": (_c_int, [_vp, _c_int, _vp, _vp, _c_int]),
+    "orbfe_kfdb_erase": (_c_int, [_vp, _c_int]),
+    "orbfe_kfdb_clear": (_c_int, [_vp]),
+    "orbfe_kfdb_size": (_c_int, [_vp]),
+    "orbfe_kfdb_shared_words": (_c_int, [_vp, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp, _vp]),
+    "orbfe_kfdb_detect_reloc": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, KF_INFO_FN, _vp, _vp, _c_int, _vp]),
 }
 
 _lib = None

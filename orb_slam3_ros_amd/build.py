@@ -11,7 +11,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SOURCES = ["orbfe_engine.hip"]
 DEPS = ["orbfe_engine.hip", "orbfe_kernels.hip", "orbfe_types.h", "glibc_sincosf.h", "stl_sort.h",
         "brief_pattern.h", "orbfe_matcher.hip", "orbfe_bow.hip", "glibc_logf.h", "glibc_atan2f.h", "orbfe_remap.hip", "orbfe_backend.hip",
-        "orbfe_rgbd.hip"]
+        "orbfe_rgbd.hip", "orbfe_kfdb.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 
@@ -73,6 +73,24 @@ def build_tracking_cpu(force: bool = False, verbose: bool = False) -> str:
             print(" ".join(cmd))
         subprocess.run(cmd, check=True)
     return TRACK_CPU_BIN
+
+
+KFDB_CPU_SRC = os.path.join(os.path.dirname(_HERE), "tests", "native", "kfdb_cpu.cpp")
+KFDB_CPU_LIB = os.path.join(os.path.dirname(_HERE), "tests", "native", "libkfdb_cpu.so")
+
+
+def build_kfdb_cpu(force: bool = False, verbose: bool = False) -> str:
+    """TEST INFRASTRUCTURE: the std::list / std::map restatement of the relocalisation side of
+    KeyFrameDatabase (tests/native/kfdb_cpu.cpp): the checker's C++ twin and the one-thread CPU
+    baseline of tools/kfdb_timing.py."""
+    if force or _stale(KFDB_CPU_LIB, [KFDB_CPU_SRC]):
+        # no contraction and no fast math: the double chain must round as the reference's
+        cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-fPIC", "-shared",
+               "-o", KFDB_CPU_LIB, KFDB_CPU_SRC]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.run(cmd, check=True)
+    return KFDB_CPU_LIB
 
 
 if __name__ == "__main__":

@@ -1522,3 +1522,6 @@ int orbfe_descriptor_distance(const uint8_t* a, const uint8_t* b) {
 
 // The RGB-D Frame: UndistortKeyPoints + ComputeStereoFromRGBD after the extraction (uses undistort_point).
 #include "orbfe_rgbd.hip"
+
+// KeyFrameDatabase for relocalisation: BowVectors resident in HBM, DetectRelocalizationCandidates.
+#include "orbfe_kfdb.hip"

@@ -1,0 +1,127 @@
+"""KeyFrameDatabase — host mirror of ORB_SLAM3::KeyFrameDatabase's relocalisation side
+(KeyFrameDatabase.cc:39-77, :733-845) over the C-ABI (orbfe_kfdb_*). Every added keyframe's
+BowVector lives in HBM; DetectRelocalizationCandidates scores the frame against all of them in
+liborbfe.so's HIP kernel and runs the covisibility tail inside the library.
+Keyframes are named by ids >= 0: indices into the caller's own keyframe table, the same table that
+holds its KeyFrameFeatures for SearchByBoWBatch.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import _lib
+
+
+def _bow(bow):
+    ids, w = bow
+    ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+    w = np.ascontiguousarray(w, np.float64).reshape(-1)
+    if len(ids) != len(w):
+        raise ValueError("a BowVector needs one weight per word id")
+    return ids, w
+
+
+def _lookup(table, kf_id, default):
+    if table is None:
+        return default
+    if callable(table):
+        return table(kf_id)
+    return table.get(kf_id, default)
+
+
+class KeyFrameDatabase:
+    def __init__(self, n_words: int):
+        self._lib = _lib.load()
+        self._h = ctypes.c_void_p()
+        _lib.check(self._lib.orbfe_kfdb_create(int(n_words), ctypes.byref(self._h)), "KeyFrameDatabase")
+        self.n_words = int(n_words)
+
+    def add(self, kf_id: int, bow) -> None:
+        """bow: the (word_ids, weights) pair ORBVocabulary.transform returns (pKF->mBowVec)."""
+        ids, w = _bow(bow)
+        _lib.check(self._lib.orbfe_kfdb_add(self._h, int(kf_id), ids.ctypes.data, w.ctypes.data, len(ids)),
+                   "KeyFrameDatabase.add")
+
+    def erase(self, kf_id: int) -> None:
+        _lib.check(self._lib.orbfe_kfdb_erase(self._h, int(kf_id)), "KeyFrameDatabase.erase")
+
+    def clear(self) -> None:
+        _lib.check(self._lib.orbfe_kfdb_clear(self._h), "KeyFrameDatabase.clear")
+
+    def __len__(self) -> int:
+        return _lib.check(self._lib.orbfe_kfdb_size(self._h), "KeyFrameDatabase.size")
+
+    def shared_words(self, bow):
+        """-> (kf_ids, words, scores, scored, maxCommonWords): lKFsSharingWords in the reference's list
+        order with mnRelocWords, and si (float32) where scored. Updates mRelocScore of the scored ones."""
+        ids, w = _bow(bow)
+        cap = max(len(self), 1)
+        while True:   # the cap protocol: another thread may add between len() and the query
+            kf = np.zeros(cap, np.int32)
+            words = np.zeros(cap, np.int32)
+            scores = np.zeros(cap, np.float32)
+            scored = np.zeros(cap, np.uint8)
+            n, mx = ctypes.c_int32(-1), ctypes.c_int32()
+            rc = self._lib.orbfe_kfdb_shared_words(self._h, ids.ctypes.data, w.ctypes.data, len(ids), kf.ctypes.data,
+                                                   words.ctypes.data, scores.ctypes.data, scored.ctypes.data, cap,
+                                                   ctypes.byref(n), ctypes.byref(mx))
+            if rc == _lib.ORBFE_E_ARG and n.value > cap:
+                cap = n.value   # nothing was written and no state changed: ask again with the needed count
+                continue
+            break
+        _lib.check(rc, "KeyFrameDatabase.shared_words")
+        n = n.value
+        return kf[:n].copy(), words[:n].copy(), scores[:n].copy(), scored[:n].astype(bool), mx.value
+
+    def DetectRelocalizationCandidates(self, bow, map_id: int = 0, neighbours=None, maps=None) -> np.ndarray:
+        """vpRelocCandidates as an int32 array of keyframe ids. neighbours: dict or callable
+        kf_id -> GetBestCovisibilityKeyFrames(10) ids (more than 10 are cut); maps: dict or callable
+        kf_id -> map id (missing: map_id). The callables must not use this database."""
+        ids, w = _bow(bow)
+        cap = max(len(self), 1)
+        # ctypes swallows an exception raised inside a callback: record the first one and re-raise it
+        # after the call, as SearchForTriangulationEpi does. After an error the callback answers -1, a
+        # count the library refuses with ORBFE_E_ARG, so the failed call commits no mRelocScore.
+        err = []
+
+        def info(ctx, kf_id, nb, mp):
+            mp[0] = int(map_id)
+            if err:
+                return -1
+            try:
+                mp[0] = int(_lookup(maps, kf_id, map_id))
+                ns = list(_lookup(neighbours, kf_id, ()))[:10]
+                for i, v in enumerate(ns):
+                    nb[i] = int(v)
+                return len(ns)
+            except BaseException as ex:  # noqa: BLE001 - re-raised below
+                err.append(ex)
+                return -1
+
+        cb = _lib.KF_INFO_FN(info) if (neighbours is not None or maps is not None) else _lib.KF_INFO_FN()
+        while True:   # the cap protocol: another thread may add between len() and the query
+            out = np.zeros(cap, np.int32)
+            n = ctypes.c_int32(-1)
+            rc = self._lib.orbfe_kfdb_detect_reloc(self._h, ids.ctypes.data, w.ctypes.data, len(ids), int(map_id), cb,
+                                                   None, out.ctypes.data, cap, ctypes.byref(n))
+            if err:
+                raise err[0]
+            if rc == _lib.ORBFE_E_ARG and n.value > cap:
+                cap = n.value   # no state changed: ask again with the needed count
+                continue
+            break
+        _lib.check(rc, "DetectRelocalizationCandidates")
+        return out[:n.value].copy()
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.orbfe_kfdb_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
