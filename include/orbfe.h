@@ -852,6 +852,25 @@ float orbfe_matcher_last_ms(void);
  * evaluated (the last one confirms convergence). ORBFE_E_ARG when the last call counted nothing. */
 int orbfe_matcher_set_stats(int enable);
 int orbfe_matcher_last_stats(long long* out);
+/* Inspection (tests only): which form the driver chose for this thread's last SearchByProjection call
+ * (local map, last frame, keyframe; host, frustum and device-resident entry points). A host record set
+ * where the driver launches; a refused or empty search reports ORBFE_SBP_FORM_NONE. */
+enum {
+    ORBFE_SBP_FORM_NONE = 0,
+    ORBFE_SBP_FORM_BLOCK = 1,     /* k_sbp_block<mode>, one workgroup */
+    ORBFE_SBP_FORM_MULTI = 2,     /* k_sbp_multi0 + k_sbp_multi */
+    ORBFE_SBP_FORM_BAND = 3,      /* k_sbp_band */
+    ORBFE_SBP_FORM_LOCAL = 4,     /* k_sbp_local */
+    ORBFE_SBP_FORM_LOCAL_WQ0 = 5, /* k_sbp_local_wq<0>: frame read in HBM */
+    ORBFE_SBP_FORM_LOCAL_WQ1 = 6, /* k_sbp_local_wq<1>: frame staged in LDS */
+    ORBFE_SBP_FORM_LOCAL_WQ2 = 7, /* k_sbp_local_wq<2>: keypoints and gates staged in LDS */
+    ORBFE_SBP_FORM_PROJ = 8,      /* k_sbp_proj + k_mt_commit_count / _drop / _write */
+    ORBFE_SBP_FORM_BLOCK4 = 9,    /* two cameras, local map, one workgroup */
+    ORBFE_SBP_FORM_BLOCK2 = 10,   /* two cameras, last frame, one workgroup */
+    ORBFE_SBP_FORM_LOCAL2 = 11,   /* two cameras, local map, multi-launch */
+    ORBFE_SBP_FORM_PROJ2 = 12     /* two cameras, last frame / keyframe, multi-launch */
+};
+int orbfe_matcher_last_form(void);
 
 /* Debug/inspection (tests only): copy an intermediate of image `image`, level `level` of the last
  * batch to host memory. what: 0 = per-cell FAST key counts (int32[n_cells]),

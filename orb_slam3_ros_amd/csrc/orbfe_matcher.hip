@@ -3534,6 +3534,8 @@ thread_local bool t_timing = false;
 // orbfe_matcher_set_stats: window candidates / Hamming pairs / passes of the last counted search
 thread_local bool t_stats = false;
 thread_local long long t_last_stats[3] = {-1, -1, -1};
+// orbfe_matcher_last_form: the form sbp_run chose for the thread's last SearchByProjection (host record)
+thread_local int t_last_form = ORBFE_SBP_FORM_NONE;
 thread_local float t_last_ms = -1.f;
 thread_local hipEvent_t t_ev[2] = {nullptr, nullptr};
 struct MsTimer {
@@ -3985,6 +3987,7 @@ int sbp_block_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* m
     const BlkIO io{mvp_in, obs_d, mvp_out, rl.stride, rl.id_off, rl.angle_off, checkOri, ntm, t_ms.hs_dev, seq,
                    stats.words, (zc && !fin && !lp) ? ms_ptr<uint4>(o_qdev) : nullptr};
     const bool two4 = F->two_cams && mode == 0;
+    t_last_form = two4 ? ORBFE_SBP_FORM_BLOCK4 : ORBFE_SBP_FORM_BLOCK;
     const size_t lds = two4 ? blk_lds(n, F->nlevels, gm, 2, blk4_bytes_per_kp()) : blk_lds(n, F->nlevels, gm);
     if (two4)
         hipLaunchKernelGGL(k_sbp_block4, dim3(1), dim3(MT_BLK_NT), lds, s, fr, gm, (const orbfe_map_point*)q, nq, th, a0,
@@ -4017,6 +4020,7 @@ int sbp_block2_run(const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs, c
                    const float* right_uv, int nq, float th, int a0, int a1, int maxDist, int checkOri,
                    const BlkGeom& gm, const LastProjIn* lp = nullptr) {
     const int n = F->n;
+    t_last_form = ORBFE_SBP_FORM_BLOCK2;
     Plan p;
     FramePlan fp;
     fp.plan(p, F, true, false);
@@ -4084,6 +4088,7 @@ int sbp_multi_run(const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs, co
                   const RecLayout& layout, float th, int a0, float thFar, float nnratio, const BlkGeom& gm,
                   const FrustumIn* fin, const DevIn* dev) {
     const int n = F->n;
+    t_last_form = ORBFE_SBP_FORM_MULTI;
     const int nbk = F->nlevels * gm.NB * gm.NS;
     RecLayout rl = layout;
     Plan p;
@@ -4226,6 +4231,7 @@ int sbp_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs
             const FrustumIn* fin = nullptr, const DevIn* dev = nullptr, const float* right_uv = nullptr,
             const LastProjIn* lp = nullptr) {
     RecLayout rl = layout;
+    t_last_form = ORBFE_SBP_FORM_NONE;   // a refused or empty search ran none
     // a device view of the current frame (orbfe_frame_device_view): the frame's arrays are read in HBM
     // by k_sbp_block; any other path would read them on the host, so other shapes are refused
     const bool fdev = F && F->device != 0;
@@ -4416,6 +4422,7 @@ int sbp_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs
                     const size_t lds = ((size_t)n * 56 + (nbk + 1) * 4 + 8 + nbk * 16 + 15) & ~(size_t)15;
                     int qshift = 0;
                     while ((((nq - 1) >> qshift) >> 7) > 0) qshift++;   // 128 query bins
+                    t_last_form = ORBFE_SBP_FORM_BAND;
                     hipLaunchKernelGGL(k_sbp_band, dim3(nb), dim3(MT_BNT), lds, s, fr, bg, (const orbfe_map_point*)q, nq,
                                        th, a0, thFar, nnratio, b0, fcur, assign, changed + pass, io, fprev, qshift);
                 } else if (mode == 0 && th >= MT_WAVE_TH) {
@@ -4424,6 +4431,7 @@ int sbp_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs
                     const size_t cellb = (MT_WNT / 64) * 64 * sizeof(int2);
                     const int st = staged ? 1 : (cellb + (size_t)n * 24 <= 150 * 1024 ? 2 : 0);
                     const size_t lds = cellb + (st == 1 ? (size_t)n * 56 : st == 2 ? (size_t)n * 24 : 0);
+                    t_last_form = ORBFE_SBP_FORM_LOCAL_WQ0 + st;
                     if (st == 1)
                         hipLaunchKernelGGL(k_sbp_local_wq<1>, dim3(nb), dim3(MT_WNT), lds, s, fr,
                                            (const orbfe_map_point*)q, nq, th, a0, thFar, nnratio, b0, fcur, assign,
@@ -4437,9 +4445,11 @@ int sbp_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs
                                            (const orbfe_map_point*)q, nq, th, a0, thFar, nnratio, b0, fcur, assign,
                                            changed + pass, io);
                 } else if (mode == 0) {
+                    t_last_form = ORBFE_SBP_FORM_LOCAL;
                     hipLaunchKernelGGL(k_sbp_local, gq, dim3(MT_NT), 0, s, fr, (const orbfe_map_point*)q, nq, th, a0,
                                        thFar, nnratio, b0, fcur, assign, changed + pass, io);
                 } else {
+                    t_last_form = ORBFE_SBP_FORM_PROJ;
                     hipLaunchKernelGGL(k_sbp_proj, gq, dim3(MT_NT), 0, s, fr, (const orbfe_proj_point*)q, nq, th,
                                        mode == 1 ? 0 : 1, a0, a1, maxDist, b0, fcur, assign, changed + pass, io);
                 }
@@ -4468,6 +4478,7 @@ int sbp_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs
         }
     }
     const int chunk = 2;   // passes launched between host checks (two-camera frames)
+    t_last_form = (two && mode == 0) ? ORBFE_SBP_FORM_LOCAL2 : ORBFE_SBP_FORM_PROJ2;
     while (true) {
         for (int c = 0; c < chunk; c++, pass++) {
             if (pass >= MT_MAX_PASSES) return ORBFE_E_CAPACITY;
@@ -5217,6 +5228,8 @@ int orbfe_matcher_last_stats(long long* out) {
     for (int i = 0; i < 3; i++) out[i] = t_last_stats[i];
     return t_last_stats[2] >= 0 ? ORBFE_OK : ORBFE_E_ARG;
 }
+
+int orbfe_matcher_last_form(void) { return t_last_form; }
 
 float orbfe_matcher_last_ms(void) { return t_last_ms; }
 

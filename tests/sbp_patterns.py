@@ -1,0 +1,677 @@
+"""Planted SearchByProjection scenes: every acceptance rule of the three single-camera forms at the value
+where it decides. Each case names its rule and carries a `check(case, trace, mvp, n)` that proves from
+the trace of oracle/sbp_definition.py that this rule decided; float-sensitive cases also carry `double`,
+which evaluates the careless (double) variant of the rule and must disagree.
+
+Descriptors are planted: a query's candidates are its own descriptor with d chosen bits flipped, so every
+Hamming distance is chosen. Geometry derives from the search radius R of the case's th and level. Queries
+that must not interact sit at sites far apart. Scenes stay below 300 keypoints and 300 queries; pad_keys /
+pad_queries append inert records up to 2,049 without moving a planted index.
+
+kind: "local" (MAP_POINT records), "lastframe" / "kf" (PROJ_POINT records), "init" (two frames).
+"""
+import numpy as np
+
+from oracle import sbp_definition as sd
+from orb_slam3_ros_amd import synth_match as sm
+from orb_slam3_ros_amd.extractor import KEYPOINT_DTYPE
+from orb_slam3_ros_amd.matcher import MAP_POINT_DTYPE, MP_IN_VIEW, PROJ_POINT_DTYPE, MatchFrame
+
+f32 = np.float32
+NLEVELS = 8
+SF = sm.scale_factors(NLEVELS)
+BOUNDS = (0.0, 752.0, 0.0, 480.0)
+MBF = float(f32(50.48))
+PAD_N = 2049
+LOCAL_TH = (1, 3, 5)
+PROJ_TH = {"lastframe": 7, "kf": 10}
+INF = f32(np.inf)
+
+
+def up(x):
+    return np.nextafter(f32(x), INF)
+
+
+def down(x):
+    return np.nextafter(f32(x), -INF)
+
+
+def base_desc(seed):
+    return np.random.default_rng(1000 + seed).integers(0, 256, 32, dtype=np.uint8)
+
+
+def flip(desc, bits):
+    """desc with the given bit positions flipped (an int d: the first d bits)."""
+    b = np.unpackbits(desc)
+    idx = np.arange(bits) if np.isscalar(bits) else np.asarray(list(bits), int)
+    b[idx] ^= 1
+    return np.packbits(b)
+
+
+def radius(kind, th, lvl):
+    """The reference's window radius in float (local map: viewCos 0.999 -> 2.5)."""
+    if kind == "local":
+        r = f32(2.5)
+        if th != 1.0:
+            r = f32(r * f32(th))
+        return f32(r * SF[lvl])
+    return f32(f32(th) * SF[lvl])
+
+
+class Case:
+    def __init__(self, name, rule, kind, F, q, mvp0, obs, check, double=None, **par):
+        self.name, self.rule, self.kind, self.F, self.q = name, rule, kind, F, q
+        self.mvp0, self.obs, self.check, self.double, self.par = mvp0, obs, check, double, par
+        assert F.N <= 300 and len(q) <= 300, name
+
+    def __repr__(self):
+        return self.name
+
+
+class Scene:
+    def __init__(self, kind, th, bounds=BOUNDS, stereo=False, nnratio=0.8, **par):
+        self.kind, self.th, self.bounds, self.stereo, self.nnratio, self.par = kind, th, bounds, stereo, nnratio, par
+        self.k, self.d, self.ur, self.q, self.held = [], [], [], [], {}
+
+    def R(self, lvl):
+        return radius(self.kind, self.th, lvl)
+
+    def kp(self, x, y, octave, desc, angle=0.0, ur=-1.0, held=None):
+        """held: (handle, observations) already in the slot."""
+        self.k.append((f32(x), f32(y), octave, f32(angle)))
+        self.d.append(desc)
+        self.ur.append(f32(ur))
+        if held is not None:
+            self.held[len(self.k) - 1] = held
+        return len(self.k) - 1
+
+    def query(self, u, v, lvl, desc, angle=0.0, obs=1, xr=0.0, invzc=0.5):
+        qid = 5000 + len(self.q)
+        if self.kind == "local":
+            r = np.zeros((), MAP_POINT_DTYPE)
+            r["proj_x"], r["proj_y"], r["proj_xr"], r["view_cos"], r["depth"] = u, v, xr, 0.999, 1.0
+            r["scale_level"], r["flags"], r["observations"], r["id"], r["desc"] = lvl, MP_IN_VIEW, obs, qid, desc
+        else:
+            r = np.zeros((), PROJ_POINT_DTYPE)
+            r["u"], r["v"], r["invzc"], r["octave"], r["angle"] = u, v, invzc, lvl, angle
+            r["valid"], r["observations"], r["id"], r["desc"] = 1, obs, qid, desc
+        self.q.append(r)
+        return len(self.q) - 1
+
+    def case(self, name, rule, check, double=None):
+        k = np.zeros(len(self.k), KEYPOINT_DTYPE)
+        for i, (x, y, o, a) in enumerate(self.k):
+            k["x"][i], k["y"][i], k["octave"][i], k["angle"][i] = x, y, o, a
+        k["size"] = 31.0 * SF[k["octave"]]
+        k["response"], k["class_id"] = 20.0, -1
+        ur = np.array(self.ur, np.float32) if self.stereo else None
+        F = MatchFrame(k, np.array(self.d, np.uint8).reshape(-1, 32), self.bounds, SF, ur, MBF)
+        mvp0 = np.full(F.N, -1, np.int32)
+        obs = np.zeros(F.N, np.int32)
+        for i, (h, o) in self.held.items():
+            mvp0[i], obs[i] = h, o
+        dt = MAP_POINT_DTYPE if self.kind == "local" else PROJ_POINT_DTYPE
+        q = np.array(self.q, dt) if self.q else np.zeros(0, dt)
+        par = dict(th=self.th, nnratio=self.nnratio, fw=False, bw=False, check_ori=False, ORBdist=100)
+        par.update(self.par)
+        return Case(f"{name}-{self.kind}-th{self.th}", rule, self.kind, F, q, mvp0, obs, check, double, **par)
+
+
+def rules_of(tr, qi):
+    return {i: r for i, r in tr["q"][qi]["cands"]}
+
+
+# ---------------------------------------------------------------- window
+def window_edge(kind, th, bounds=BOUNDS, name="window-edge", off=(0.0, 0.0)):
+    """|dx| == R exactly is out (strict <), one float inside is in; x and y, both signs."""
+    s = Scene(kind, th, bounds)
+    R = s.R(0)
+    exp = []
+    for j, (ax, sg) in enumerate([(0, 1), (0, -1), (1, 1), (1, -1)]):
+        u, v = f32(150.0 + 150 * j + off[0]), f32(200.0 + off[1])
+        b = base_desc(j)
+        c = [u, v]
+        c[ax] = f32(c[ax] + sg * R)
+        assert abs(f32(c[ax] - (u, v)[ax])) == R   # exactly on the edge
+        out = s.kp(c[0], c[1], 0, b)               # distance 0: wins if the edge is let in
+        while not abs(f32(c[ax] - (u, v)[ax])) < R:   # the first float whose float difference is inside
+            c[ax] = down(c[ax]) if sg > 0 else up(c[ax])
+        inn = s.kp(c[0], c[1], 0, flip(b, 10))
+        exp.append((s.query(u, v, 0, b), out, inn))
+
+    def check(case, tr, mvp, n):
+        for qi, out, inn in exp:
+            r = rules_of(tr, qi)
+            assert r[out] == "box" and r[inn] == "best" and tr["q"][qi]["outcome"] == "kept"
+            assert mvp[out] == -1 and mvp[inn] == case.q["id"][qi]
+        assert n == 4
+    return s.case(name, "box: |d| < r strict", check)
+
+
+def window_cells(kind, th):
+    """Window cell bounds: (x - minX - r) * invW an exact integer; overhang of every grid edge; a window
+    wholly past the last cell; a keypoint PosInGrid rejects."""
+    s = Scene(kind, th)
+    R = s.R(0)
+    invw = f32(64) / f32(752)
+    # a projection whose window's left cell coordinate is an exact integer k in float while the double
+    # product lies below k (floor would give k - 1)
+    x = kcell = None
+    for k in range(20, 44):
+        c = f32(f32(k) / invw)
+        for c in [c] + [c := down(c) for _ in range(8)]:
+            xc = f32(c + R)
+            if f32(c * invw) == k and float(c) * float(invw) < k and f32(xc - R) == c and x is None:
+                x, kcell = xc, k
+    assert x is not None, "no exact-integer projection found"
+    exp = []
+    b = base_desc(10)
+    exp.append((s.query(x, 100.0, 0, b), s.kp(x, 100.0, 0, flip(b, 5)), "exact"))
+    for j, (u, v) in enumerate([(1.0, 200.0), (745.0, 300.0), (400.0, 1.0), (500.0, 474.0)]):
+        b = base_desc(11 + j)
+        ku, kv = f32(u + (0.5 if u < 700 else -0.5)), f32(v + (0.5 if v < 400 else -0.5))
+        exp.append((s.query(u, v, 0, b), s.kp(ku, kv, 0, flip(b, 5)), "overhang"))
+    b = base_desc(20)
+    gone = s.kp(751.5, 150.0, 0, flip(b, 5))   # round(751.5 * 64 / 752) = 64: not in the grid
+    q_gone = s.query(751.0, 150.0, 0, b)
+    q_past = None
+    if kind != "lastframe":   # the last-frame form's projection rejects u > mnMaxX before the window
+        q_past = s.query(f32(752.0 + float(R) + 1.0), 400.0, 0, base_desc(21))
+        s.kp(751.0, 400.0, 0, base_desc(21))
+
+    def check(case, tr, mvp, n):
+        g = sd.PyGrid(case.F)
+        assert g.cell_range(x, 100.0, R)[0] == kcell
+        for qi, kp, _ in exp:
+            assert rules_of(tr, qi)[kp] == "best" and mvp[kp] == case.q["id"][qi]
+        assert gone not in g.cell_of and tr["q"][q_gone]["cands"] == [] and mvp[gone] == -1
+        if q_past is not None:
+            assert g.cell_range(case.q["proj_x" if kind == "local" else "u"][q_past], 400.0, R) is None
+            assert tr["q"][q_past]["cands"] == []
+        assert n == len(exp)
+    return s.case("window-cells", "cell range: exact integer, overhang, past the last cell, PosInGrid", check)
+
+
+def window_offset_bounds(kind, th):
+    """Bounds that do not start at 0 (an undistorted image): the edge case again, some keypoints at negative
+    coordinates."""
+    return window_edge(kind, th, (-160.0, 592.0, -210.0, 270.0), "window-offset-bounds", (-158.0, -208.0))
+
+
+# ---------------------------------------------------------------- level range
+def level_range(kind, th, lvl, fw=False, bw=False):
+    s = Scene(kind, th, fw=fw, bw=bw)
+    b = base_desc(30 + lvl)
+    if kind == "local":
+        lo, hi = lvl - 1, lvl
+    elif fw:
+        lo, hi = lvl, NLEVELS - 1   # from nLastOctave up; at octave 0 GetFeaturesInArea checks no level at all
+    elif bw:
+        lo, hi = 0, lvl
+    else:
+        lo, hi = lvl - 1, lvl + 1
+    u, v = f32(376.0), f32(240.0)
+    kps = {}
+    for o in range(NLEVELS):
+        inside = lo <= o <= hi
+        kps[o] = s.kp(u + f32(0.25) * o, v, o, flip(b, (20 + o) if inside else o))
+    qi = s.query(u, v, lvl, b)
+    best = min((o for o in kps if lo <= o <= hi), key=lambda o: 20 + o)
+
+    def check(case, tr, mvp, n):
+        r = rules_of(tr, qi)
+        for o, i in kps.items():
+            assert (r[i] == "level") == (not lo <= o <= hi), (o, r[i])
+        assert r[kps[best]] == "best" and mvp[kps[best]] == case.q["id"][qi] and n == 1
+    mode = "fw" if fw else "bw" if bw else "std"
+    return s.case(f"level-range-L{lvl}-{mode}", f"level range [{lo}, {hi}]", check)
+
+
+# ---------------------------------------------------------------- enumeration order on ties
+def tie_order(kind, th, dup):
+    """Three equal best distances around a point where four grid cells meet: cell-column-major order (the
+    reference's), row-major order and index order each pick a different keypoint. dup: all on one level at
+    distance 0 (accepted: 0 > nnratio * 0 is false); else the runner-up is on another level."""
+    s = Scene(kind, th)
+    b = base_desc(40)
+    x0, y0 = f32(20.5 * 11.75), f32(20.5 * 10.0)   # corner of cells (20, 20), (21, 20), (20, 21), (21, 21)
+    lvl = 1
+    d = 0 if dup else 20
+    S = s.kp(x0 + f32(1), y0 + f32(1), lvl, flip(b, d))                    # index first: cell (21, 21)
+    Q = s.kp(x0 + f32(1), y0 - f32(1), lvl if dup else lvl - 1, flip(b, d))   # row-major first: cell (21, 20)
+    P = s.kp(x0 - f32(1), y0 + f32(1), lvl, flip(b, d))                    # column-major first: cell (20, 21)
+    qi = s.query(x0, y0, lvl, b)
+
+    def check(case, tr, mvp, n):
+        g = sd.PyGrid(case.F)
+        assert (g.cell_of[P], g.cell_of[Q], g.cell_of[S]) == ((20, 21), (21, 20), (21, 21))
+        t = tr["q"][qi]
+        assert [i for i, _ in t["cands"]] == [P, Q, S]
+        assert t["best"] == P and t["bd"] == d and t["outcome"] == "kept"
+        if kind == "local":
+            assert t["bd2"] == d and (t["bl"] == t["bl2"]) == dup
+        assert mvp[P] == case.q["id"][qi] and mvp[Q] == -1 and mvp[S] == -1 and n == 1
+    return s.case("tie-dup-zero" if dup else "tie-levels", "strict <: the first enumerated of equals wins", check)
+
+
+# ---------------------------------------------------------------- distance
+def distance_edge(kind, th, lim=100):
+    s = Scene(kind, th, ORBdist=lim)
+    exp = []
+    for j, d in enumerate((lim, lim + 1)):
+        b = base_desc(50 + j)
+        u = f32(200.0 + 200 * j)
+        exp.append((s.query(u, 200.0, 0, b), s.kp(u, 200.0, 0, flip(b, d)), d <= lim))
+    b = base_desc(52)
+    blocked = s.kp(600.0, 200.0, 0, b, held=(77, 3))   # a query whose only candidate is blocked
+    qb = s.query(600.0, 200.0, 0, b)
+
+    def check(case, tr, mvp, n):
+        for qi, kp, ok in exp:
+            t = tr["q"][qi]
+            assert t["best"] == kp and t["outcome"] == ("kept" if ok else "distance")
+            assert mvp[kp] == (case.q["id"][qi] if ok else -1)
+        assert rules_of(tr, qb)[blocked] == "blocked" and tr["q"][qb]["outcome"] == "none" and mvp[blocked] == 77
+        assert n == 1
+    return s.case(f"distance-{lim}", f"bestDist <= {lim}", check)
+
+
+# ---------------------------------------------------------------- ratio (local map only)
+def ratio_cases(th, nnratio):
+    s = Scene("local", th, nnratio=nnratio)
+    pairs = []
+    # the largest accepted and the smallest rejected best distance against a second best of 100
+    acc = max(d for d in range(1, 101) if not sd.ratio_rejects(d, 100, nnratio))
+    pairs += [(acc, 100, True, False), (acc + 1, 100, False, False)]
+    # pairs on which float and double evaluation disagree: the first three found, and at 0.7 the pair
+    # (63, 90), which float accepts and double rejects
+    sens = [(d, d2) for d2 in range(2, 143) for d in range(1, min(d2, 101))
+            if sd.ratio_rejects(d, d2, nnratio) != sd.ratio_rejects(d, d2, nnratio, double=True)]
+    if nnratio == 0.75:
+        pairs.append((75, 100, True, False))
+    if nnratio == 0.8:
+        pairs.append((80, 100, True, False))
+    pairs += [(d, d2, not sd.ratio_rejects(d, d2, nnratio), True) for d, d2 in sens[:3]]
+    if nnratio == 0.7:
+        assert (63, 90) in sens and (63, 90) not in sens[:3]
+        pairs.append((63, 90, True, True))
+    exp = []
+    for j, (d, d2, ok, sensitive) in enumerate(pairs):
+        b = base_desc(60 + j)
+        u, v = f32(100.0 + 90 * (j % 7)), f32(100.0 + 100 * (j // 7))
+        k1 = s.kp(u, v, 0, flip(b, d))
+        s.kp(u + f32(0.5), v, 0, flip(b, range(256 - d2, 256)))   # other bits: d2 from the query
+        exp.append((s.query(u, v, 0, b), k1, d, d2, ok, sensitive))
+    # second best on another level: the ratio is not applied; no second best: bestDist2 stays 256
+    b = base_desc(80)
+    ko = s.kp(100.0, 400.0, 1, flip(b, 90))
+    s.kp(100.5, 400.0, 0, flip(b, range(256 - 91, 256)))
+    qo = s.query(100.0, 400.0, 1, b)
+    b = base_desc(81)
+    kn = s.kp(300.0, 400.0, 0, flip(b, 100))
+    qn = s.query(300.0, 400.0, 0, b)
+
+    def check(case, tr, mvp, n):
+        for qi, k1, d, d2, ok, _ in exp:
+            t = tr["q"][qi]
+            assert (t["best"], t["bd"], t["bd2"], t["bl"] == t["bl2"]) == (k1, d, d2, True)
+            assert t["outcome"] == ("kept" if ok else "ratio") and mvp[k1] == (case.q["id"][qi] if ok else -1)
+        if nnratio == 0.7:   # the float-only pair is planted and kept
+            assert [ok for _, _, d, d2, ok, _ in exp if (d, d2) == (63, 90)] == [True]
+        t = tr["q"][qo]
+        assert (t["bd"], t["bd2"]) == (90, 91) and t["bl"] != t["bl2"] and t["outcome"] == "kept" and mvp[ko] >= 0
+        assert sd.ratio_rejects(90, 91, nnratio)   # it would have been rejected on one level
+        t = tr["q"][qn]
+        assert (t["bd"], t["bd2"], t["bl2"]) == (100, 256, -1) and t["outcome"] == "kept" and mvp[kn] >= 0
+
+    def double(case):
+        return [sd.ratio_rejects(d, d2, nnratio, double=True) != (not ok) for _, _, d, d2, ok, sv in exp if sv]
+    return s.case(f"ratio-{nnratio}", "bestDist > nnratio * bestDist2 in float, same level only", check,
+                  double if any(e[5] for e in exp) else None)
+
+
+# ---------------------------------------------------------------- stereo
+def stereo_edge(kind, th):
+    """er == radius exactly stays (the rule is er > radius), one float over goes; uR of 0 and -1 skip the test."""
+    s = Scene(kind, th, stereo=True)
+    R = s.R(0)
+    exp = []
+    for j, mode in enumerate(("eq", "over", "zero", "minus")):
+        b = base_desc(90 + j)
+        u, v = f32(150.0 + 150 * j), f32(200.0)
+        pur = f32(100.0) if kind == "local" else sd.py_ur(u, MBF, 0.5)   # the point's predicted uR
+        ur = {"eq": f32(pur - R), "over": down(f32(pur - R)), "zero": f32(0.0), "minus": f32(-1.0)}[mode]
+        if mode == "eq":
+            assert abs(f32(pur - ur)) == R
+        if mode == "over":
+            assert abs(f32(pur - ur)) > R
+        exp.append((s.query(u, v, 0, b, xr=pur), s.kp(u, v, 0, flip(b, 5), ur=ur), mode))
+
+    def check(case, tr, mvp, n):
+        for qi, kp, mode in exp:
+            assert rules_of(tr, qi)[kp] == ("uR" if mode == "over" else "best"), mode
+            assert mvp[kp] == (-1 if mode == "over" else case.q["id"][qi])
+        assert n == 3
+    return s.case("stereo-edge", "uR > 0 and er > radius", check)
+
+
+def stereo_fused(th):
+    """Last frame: u - mbf * invzc differs by one float between two roundings and a fused multiply-subtract;
+    the keypoint's uR puts the two on opposite sides of radius."""
+    s = Scene("lastframe", th, stereo=True)
+    R = s.R(0)
+    rng = np.random.default_rng(7)
+    exp = []
+    while len(exp) < 4:
+        u, iz = f32(rng.uniform(100, 650)), f32(rng.uniform(0.05, 1.0))
+        a, c = sd.py_ur(u, MBF, iz), sd.py_ur(u, MBF, iz, fused=True)
+        if a == c or a < 1:
+            continue
+        for ur in (f32(a - R), f32(a + R), f32(c - R), f32(c + R)):
+            ea, ec = abs(f32(a - ur)) > R, abs(f32(c - ur)) > R
+            if ur > 0 and ea != ec:
+                b = base_desc(100 + len(exp))
+                v = f32(60.0 + 100 * len(exp))
+                exp.append((s.query(u, v, 0, b, invzc=iz), s.kp(u, v, 0, flip(b, 5), ur=ur), bool(ea), bool(ec)))
+                break
+
+    def check(case, tr, mvp, n):
+        for qi, kp, ea, _ in exp:
+            assert rules_of(tr, qi)[kp] == ("uR" if ea else "best")
+            assert (mvp[kp] == -1) == ea
+
+    def double(case):
+        return [ea != ec for _, _, ea, ec in exp]
+    return s.case("stereo-fused", "ur = u - mbf * invzc: product and difference each rounded to float", check, double)
+
+
+# ---------------------------------------------------------------- blocking chains
+LADDER = 13
+
+
+def ladder(kind, th, obs):
+    """Point i's nearest keypoint is K[i-1], taken by point i-1; its second choice is K[i]: the result of
+    every point depends on the one before (12 sequential dependencies). obs == 0: a holder without
+    observations blocks nobody (local map, last frame): point 1 overwrites point 0's slot and both count."""
+    s = Scene(kind, th, check_ori=(kind != "local"))
+    b = base_desc(110)
+    u, v = f32(376.0), f32(240.0)
+    blk = lambda j: range(16 * j, 16 * j + 16)   # noqa: E731
+    K = [s.kp(u + f32(0.125) * (j % 4), v + f32(0.125) * (j // 4), 0, flip(b, blk(j))) for j in range(LADDER)]
+    Q = []
+    for j in range(LADDER):
+        bits = list(range(16 * j, 16 * j + 6))   # 10 from K[j], 22 from the others ...
+        if j:
+            bits += list(range(16 * (j - 1), 16 * (j - 1) + 12))   # ... 10 from K[j-1], 22 from K[j], 34 else
+        Q.append(s.query(u, v, 0, flip(b, bits), obs=obs))
+    free = obs == 0 and kind != "kf"
+
+    def check(case, tr, mvp, n):
+        ids = case.q["id"]
+        assert tr["q"][Q[0]]["best"] == K[0]
+        if free:   # 1 overwrites 0 on K[0]; from then on point j finds K[j-1] free
+            for j in range(1, LADDER):
+                assert tr["q"][Q[j]]["best"] == K[j - 1] and tr["q"][Q[j]]["bd"] == 10
+            assert [mvp[k] for k in K] == [ids[Q[j + 1]] for j in range(LADDER - 1)] + [-1]
+        else:
+            for j in range(1, LADDER):   # each step needs the step before: LADDER - 1 >= 12 dependencies
+                assert rules_of(tr, Q[j])[K[j - 1]] == "blocked" and case.mvp0[K[j - 1]] == -1
+                assert tr["q"][Q[j]]["best"] == K[j] and tr["q"][Q[j]]["bd"] == 22
+            assert [mvp[k] for k in K] == [ids[q] for q in Q]
+        assert n == LADDER and LADDER - 1 >= 12
+    return s.case(f"ladder-obs{obs}", "blocked: a held slot with Observations() > 0 (keyframe: any held slot)", check)
+
+
+def preheld(kind, th):
+    """A slot held before the search by a point without observations: free for the local map and the last
+    frame, blocked for the keyframe form."""
+    s = Scene(kind, th)
+    b = base_desc(120)
+    k0 = s.kp(300.0, 200.0, 0, flip(b, 5), held=(77, 0))
+    q0 = s.query(300.0, 200.0, 0, b)
+    b = base_desc(121)
+    k1 = s.kp(500.0, 200.0, 0, flip(b, 5), held=(78, 2))
+    q1 = s.query(500.0, 200.0, 0, b)
+
+    def check(case, tr, mvp, n):
+        assert rules_of(tr, q0)[k0] == ("blocked" if kind == "kf" else "best")
+        assert mvp[k0] == (77 if kind == "kf" else case.q["id"][q0])
+        assert rules_of(tr, q1)[k1] == "blocked" and mvp[k1] == 78
+        assert n == (0 if kind == "kf" else 1)
+    return s.case("preheld-obs0", "blocked: Observations() == 0 frees a slot except in the keyframe form", check)
+
+
+# ---------------------------------------------------------------- rotation
+HALF = (15.0, 45.0, 105.0, 165.0, 195.0, 225.0, 255.0, 315.0, 345.0)
+
+
+def _plans():
+    """name -> list of (query angle, keypoint angle, bin by the float rule), one entry per matched pair."""
+    def centre(counts):
+        return [(f32(30.0 * b), f32(0.0), b) for b, c in counts.items() for _ in range(c)]
+    p = {"ties": centre({2: 5, 7: 5, 11: 5, 12: 5, 4: 2}),   # strict >: the earlier bin keeps its place
+         "one-bin": centre({5: 4}), "two-bins": centre({5: 4, 6: 1}), "zero-bins": []}
+    for m in (10, 30, 60):   # max2 == max3 == max1 / 10: kept in float, dropped with 0.1f as a double
+        p[f"tenth-{m}"] = centre({3: m, 9: m // 10, 12: m // 10, 6: max(m // 10 - 1, 0)})
+    # one float below k * 30 + 15: rot * (1.0f / 30) is exactly k + 0.5 and rounds up, rot / 30 does not
+    half = [(down(a), f32(0.0), int(a // 30) + 1) for a in HALF]
+    p["half-way"] = half + centre({1: 5, 4: 5, 8: 5})
+    p["angles"] = [(down(360.0), f32(0.0), 12),     # just below 360
+                   (f32(0.0), f32(-1.0), 0),        # keypoint angle -1 (OpenCV's default): rot 1
+                   (f32(-1.0), f32(0.0), 12),       # rot -1 + 360
+                   (f32(900.0), f32(0.0), 0),       # out of range: round(rot / 30) == 30 wraps to bin 0
+                   (f32(10.0), f32(350.0), 1)]      # negative difference: 20
+    return p
+
+
+PLANS = _plans()
+
+
+def _plan_bins(plan):
+    bins = [0] * sd.HISTO_LENGTH
+    for _, _, b in plan:
+        bins[b] += 1
+    return bins
+
+
+def _site(j):
+    return f32(20.0 + 24 * (j % 30)), f32(20.0 + 40 * (j // 30))
+
+
+def rotation(kind, th, pname, check_ori):
+    s = Scene(kind, th, check_ori=check_ori)
+    plan = PLANS[pname]
+    exp = []
+    for j, (aq, ak, bn) in enumerate(plan):
+        assert 0 <= bn < sd.HISTO_LENGTH
+        b = base_desc(200 + j)
+        u, v = _site(j)
+        exp.append((s.query(u, v, 0, b, angle=aq), s.kp(u, v, 0, flip(b, 3), angle=ak), bn))
+    if not plan:   # zero non-empty bins: candidates that miss the distance rule
+        for j in range(3):
+            b = base_desc(200 + j)
+            u, v = _site(j)
+            s.kp(u, v, 0, flip(b, 120), angle=0.0)
+            s.query(u, v, 0, b, angle=90.0)
+    bins = _plan_bins(plan)
+    keep = sd.py_three_maxima(bins)
+
+    def check(case, tr, mvp, n):
+        if check_ori:
+            assert tr["bins"] == bins and tr["kept_bins"] == keep
+        else:
+            assert tr["bins"] is None
+        for qi, kp, bn in exp:
+            kept = (not check_ori) or bn in keep
+            assert tr["q"][qi]["outcome"] == ("kept" if kept else "dropped bin")
+            assert mvp[kp] == (case.q["id"][qi] if kept else -1)
+        assert n == (sum(bins[b] for b in keep if b >= 0) if check_ori else len(plan))
+
+    def double(case):
+        if pname.startswith("tenth"):
+            return [sd.py_three_maxima(bins, double=True) != keep]
+        return [sd.py_rot_bin(aq, ak, double=True) != bn for aq, ak, bn in plan[:len(HALF)]]
+    sens = check_ori and (pname.startswith("tenth") or pname == "half-way")
+    return s.case(f"rot-{pname}-ori{int(check_ori)}", "dropped bin: float rot * (1.0f / 30), max < 0.1f * (float)max1",
+                  check, double if sens else None)
+
+
+class InitCase:
+    """SearchForInitialization over a bin plan: F1 / F2 share positions, pair j matches at distance 3."""
+
+    def __init__(self, pname):
+        plan = PLANS[pname]
+        self.name, self.rule = f"rot-{pname}-init", "dropped bin (k_init_commit)"
+        n = max(len(plan), 1)
+        k1 = np.zeros(n, KEYPOINT_DTYPE)
+        k1["size"], k1["response"], k1["class_id"] = 31.0, 20.0, -1
+        k2 = k1.copy()
+        d1 = np.zeros((n, 32), np.uint8)
+        d2 = np.zeros((n, 32), np.uint8)
+        for j in range(n):
+            u, v = _site(j)
+            k1["x"][j] = k2["x"][j] = u
+            k1["y"][j] = k2["y"][j] = v
+            d1[j] = base_desc(200 + j)
+            d2[j] = flip(d1[j], 3 if plan else 120)
+            if plan:
+                k1["angle"][j], k2["angle"][j] = plan[j][0], plan[j][1]
+        self.F1 = MatchFrame(k1, d1, BOUNDS, SF)
+        self.F2 = MatchFrame(k2, d2, BOUNDS, SF)
+        self.bins = _plan_bins(plan)
+        keep = sd.py_three_maxima(self.bins)
+        self.expect = np.array([j if plan[j][2] in keep else -1 for j in range(len(plan))] or [-1], np.int32)
+
+    def prev(self):
+        return np.stack([self.F1.keys["x"], self.F1.keys["y"]], 1).astype(np.float32)
+
+    def __repr__(self):
+        return self.name
+
+
+# ---------------------------------------------------------------- padding
+def pad_keys(case, n=PAD_N):
+    """Inert keypoints up to n: half outside the grid bounds, half inside at the corner farthest from every
+    query, outside every query's box, on an octave no query's level range reaches where one exists."""
+    F = case.F
+    add = n - F.N
+    k = np.zeros(add, KEYPOINT_DTYPE)
+    rng = np.random.default_rng(5)
+    qx = case.q["proj_x" if case.kind == "local" else "u"]
+    qy = case.q["proj_y" if case.kind == "local" else "v"]
+    lv = case.q["scale_level" if case.kind == "local" else "octave"]
+    x0, x1, y0, y1 = F.bounds
+    corners = [(x0 + 3, y0 + 3), (x1 - 14, y0 + 3), (x0 + 3, y1 - 12), (x1 - 14, y1 - 12)]
+    cx, cy = max(corners, key=lambda c: min([max(abs(c[0] - a), abs(c[1] - b)) for a, b in zip(qx, qy)] or [1e9]))
+    Rmax = max([float(radius(case.kind, case.par["th"], int(v))) for v in lv] or [0.0])
+    assert all(max(abs(cx - a), abs(cy - b)) > Rmax + 8 for a, b in zip(qx, qy)), case.name
+    reach = set()
+    for v in lv:
+        reach |= set(range(NLEVELS)) if case.kind != "local" and case.par["fw"] else {int(v) - 1, int(v), int(v) + 1}
+    quiet = [o for o in range(NLEVELS) if o not in reach]
+    half = add // 2
+    k["x"][:half] = x1 + 40 + rng.uniform(0, 50, half)   # PosInGrid false
+    k["y"][:half] = rng.uniform(y0, y1, half)
+    k["x"][half:] = cx + rng.uniform(0, 5, add - half)
+    k["y"][half:] = cy + rng.uniform(0, 5, add - half)
+    k["octave"] = quiet[-1] if quiet else NLEVELS - 1
+    k["size"], k["response"], k["class_id"] = 31.0, 20.0, -1
+    desc = rng.integers(0, 256, (add, 32), dtype=np.uint8)
+    ur = None if F.uright is None else np.concatenate([F.uright, np.full(add, -1, np.float32)])
+    F2 = MatchFrame(np.concatenate([F.keys, k]), np.concatenate([F.desc, desc]), F.bounds, SF, ur, MBF)
+    c = object.__new__(Case)   # past the planted-scene size limit on purpose
+    c.__dict__.update(case.__dict__)
+    c.name, c.F = case.name + "+keys", F2
+    c.mvp0 = np.concatenate([case.mvp0, np.full(add, -1, np.int32)])
+    c.obs = np.concatenate([case.obs, np.zeros(add, np.int32)])
+    return c
+
+
+def pad_queries(case, n=PAD_N):
+    """Inert queries up to n (flags 0 / valid 0, every other field as a live record's)."""
+    add = n - len(case.q)
+    rng = np.random.default_rng(6)
+    q = np.zeros(add, case.q.dtype)
+    x0, x1, y0, y1 = case.F.bounds
+    q["proj_x" if case.kind == "local" else "u"] = rng.uniform(x0, x1, add)
+    q["proj_y" if case.kind == "local" else "v"] = rng.uniform(y0, y1, add)
+    q["scale_level" if case.kind == "local" else "octave"] = rng.integers(0, NLEVELS, add)
+    q["observations"], q["id"] = 1, 9000 + np.arange(add)
+    q["desc"] = rng.integers(0, 256, (add, 32), dtype=np.uint8)
+    if case.kind == "local":
+        q["view_cos"] = 0.999
+    else:
+        q["invzc"] = 0.5
+    c = object.__new__(Case)
+    c.__dict__.update(case.__dict__)
+    c.name, c.q = case.name + "+queries", np.concatenate([case.q, q])
+    return c
+
+
+# ---------------------------------------------------------------- the list
+def _build():
+    out = []
+    for kind in ("local", "lastframe", "kf"):
+        for th in (LOCAL_TH if kind == "local" else (PROJ_TH[kind],)):
+            out += [window_edge(kind, th), window_cells(kind, th), window_offset_bounds(kind, th)]
+            for lvl in (0, 1, NLEVELS - 1):
+                out.append(level_range(kind, th, lvl))
+            if kind == "lastframe":
+                for lvl in (0, NLEVELS - 1):
+                    out += [level_range(kind, th, lvl, fw=True), level_range(kind, th, lvl, bw=True)]
+            out += [tie_order(kind, th, False), tie_order(kind, th, True)]
+            out.append(distance_edge(kind, th, 100))
+            if kind == "kf":
+                out.append(distance_edge(kind, th, 80))
+            if kind == "local":
+                out += [ratio_cases(th, r) for r in (0.6, 0.7, 0.75, 0.8, 0.9)]
+            if kind != "kf":
+                out.append(stereo_edge(kind, th))
+            if kind == "lastframe":
+                out.append(stereo_fused(th))
+            out += [ladder(kind, th, 1), ladder(kind, th, 0), preheld(kind, th)]
+            if kind != "local":
+                for pname in PLANS:
+                    out += [rotation(kind, 1, pname, True), rotation(kind, 1, pname, False)]
+    assert len({c.name for c in out}) == len(out)
+    return out
+
+
+_CASES = None
+
+
+def all_cases():
+    global _CASES
+    if _CASES is None:
+        _CASES = _build()
+    return _CASES
+
+
+def init_cases():
+    return [InitCase(p) for p in PLANS]
+
+
+# ---------------------------------------------------------------- running a case
+def run_definition(case):
+    """-> (nmatches, trace, slots) by oracle/sbp_definition.py, tracing on."""
+    mvp, p = case.mvp0.copy(), case.par
+    if case.kind == "local":
+        n, tr = sd.py_sbp_local(case.F, mvp, case.obs, case.q, p["th"], p["nnratio"], trace=True)
+    elif case.kind == "lastframe":
+        n, tr = sd.py_sbp_lastframe(case.F, mvp, case.obs, case.q, p["th"], p["fw"], p["bw"], p["check_ori"], trace=True)
+    else:
+        n, tr = sd.py_sbp_kf(case.F, mvp, case.q, p["th"], p["ORBdist"], p["check_ori"], trace=True)
+    return n, tr, mvp
+
+
+def run_oracle(oracle_lib, case):
+    """-> (nmatches, slots) by the C++ oracle."""
+    mvp, p = case.mvp0.copy(), case.par
+    om = oracle_lib.OracleMatcher(p["nnratio"], p["check_ori"])
+    if case.kind == "local":
+        n = om.sbp_local(case.F, mvp, case.obs, case.q, p["th"])
+    elif case.kind == "lastframe":
+        n = om.sbp_lastframe(case.F, mvp, case.obs, case.q, p["th"], p["fw"], p["bw"])
+    else:
+        n = om.sbp_kf(case.F, mvp, case.q, p["th"], p["ORBdist"])
+    return n, mvp
