@@ -754,6 +754,40 @@ int orbfe_vocabulary_transform(const orbfe_vocabulary* voc, const uint8_t* desc,
                                uint32_t* bow_word_ids, double* bow_weights, int32_t* bow_n,
                                uint32_t* fv_node_ids, int32_t* fv_offsets, uint32_t* fv_indices, int32_t* fv_n);
 
+/* The same transform for nimg images that already sit in HBM, as one stream-ordered stage. The result
+ * of image i is rows i of these caller-owned device arrays (row stride cap; fv_offsets cap + 1):
+ * counts[i] = {bow_n, fv_n}, entries past an image's counts unspecified (the fv rows are the call's
+ * scratch). counts[i] = {-1, -1}: image i's input count was outside [0, cap]; nothing else of that
+ * image is read or written. */
+typedef struct orbfe_bow_batch {      /* device pointers, caller-owned, row stride cap */
+    uint32_t* bow_word_ids;           /* [nimg][cap]     */
+    double*   bow_weights;            /* [nimg][cap]     */
+    uint32_t* fv_node_ids;            /* [nimg][cap]     */
+    int32_t*  fv_offsets;             /* [nimg][cap + 1] */
+    uint32_t* fv_indices;             /* [nimg][cap]     */
+    int32_t*  counts;                 /* [nimg][2] = {bow_n, fv_n}; {-1,-1}: bad input count */
+} orbfe_bow_batch;
+
+/* d_desc [nimg][cap][32] and image i's count at d_counts[i * count_stride], both device memory (the
+ * layout of orbfe_batch_outputs with count_stride = 2: its second int, monoIndex, is not read). The
+ * counts are read on the device: the call makes no host wait and no allocation, and needs no
+ * workspace (stream = hipStream_t or NULL). Bit-identical per image to orbfe_vocabulary_transform.
+ * cap <= 8192. ORBFE_E_ARG before any device call: nimg < 0, cap <= 0, count_stride < 1, a NULL
+ * pointer, a pointer that is not aligned to its element (d_desc: 4 bytes); ORBFE_E_CAPACITY:
+ * cap > 8192; nimg == 0: ORBFE_OK. ORBFE_E_ARG with another device current than the vocabulary's. An
+ * empty vocabulary (no words) gives {0, 0} for every image. */
+int orbfe_vocabulary_transform_batch(const orbfe_vocabulary* voc, const uint8_t* d_desc, const int32_t* d_counts,
+                                     int32_t count_stride, int32_t nimg, int32_t cap, int32_t levelsup,
+                                     const orbfe_bow_batch* out, void* stream);
+
+/* Frame::ComputeBoW for one frame (the Tracking thread's call): F is a host view or the view of
+ * orbfe_frame_device_view, whose descriptors are read in HBM; only F->n, F->desc and F->device are
+ * read. F->n <= 8192 (ORBFE_E_CAPACITY above). Host outputs as orbfe_vocabulary_transform's. One host
+ * wait: the result comes back as one block. */
+int orbfe_frame_compute_bow(const orbfe_vocabulary* voc, const orbfe_frame* F, int32_t levelsup,
+                            uint32_t* bow_word_ids, double* bow_weights, int32_t* bow_n,
+                            uint32_t* fv_node_ids, int32_t* fv_offsets, uint32_t* fv_indices, int32_t* fv_n);
+
 /* ---------------------------------------------------------------------------------------------
  * KeyFrameDatabase for relocalisation (KeyFrameDatabase.cc:39-77, :733-845): the one method of the
  * keyframe database that Tracking calls, Tracking::Relocalization's DetectRelocalizationCandidates.
@@ -783,6 +817,14 @@ void orbfe_kfdb_destroy(orbfe_kfdb* db);                    /* NULL is a no-op; 
  * can never share a word). The keyframe goes to the back of every word's list: entries are ordered
  * by their add, so erase followed by add moves a keyframe to the back. The arrays are free on return. */
 int orbfe_kfdb_add(orbfe_kfdb* db, int32_t kf_id, const uint32_t* word_ids, const double* weights, int32_t n);
+/* add for the images of a transformed batch, device to device: image i's BowVector becomes keyframe
+ * kf_ids[i], in order i = 0..nimg-1 (kf_ids[i] < 0 skips image i). Waits for `stream` (the batch's),
+ * downloads the counts and nothing else, makes room once and copies in one launch. ORBFE_E_ARG with
+ * no state changed: voc's word count differs from the database's, an id that repeats or is present,
+ * an image to add whose counts are {-1, -1}. The word ids are trusted (ascending and below the word
+ * count by construction). bows' arrays are free on return. */
+int orbfe_kfdb_add_batch(orbfe_kfdb* db, const orbfe_vocabulary* voc, const int32_t* kf_ids,
+                         const orbfe_bow_batch* bows, int32_t nimg, int32_t cap, void* stream);
 int orbfe_kfdb_erase(orbfe_kfdb* db, int32_t kf_id);        /* KeyFrameDatabase::erase */
 int orbfe_kfdb_clear(orbfe_kfdb* db);                       /* KeyFrameDatabase::clear */
 int orbfe_kfdb_size(const orbfe_kfdb* db);                  /* keyframes present */

@@ -46,6 +46,12 @@ class RGBDParamsStruct(ctypes.Structure):
                 ("depth_factor", ctypes.c_float)]
 
 
+class BowBatchStruct(ctypes.Structure):
+    """orbfe_bow_batch: six device pointers."""
+    _fields_ = [("bow_word_ids", ctypes.c_void_p), ("bow_weights", ctypes.c_void_p), ("fv_node_ids", ctypes.c_void_p),
+                ("fv_offsets", ctypes.c_void_p), ("fv_indices", ctypes.c_void_p), ("counts", ctypes.c_void_p)]
+
+
 _c_int, _c_float, _vp = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 _P_int, _P_float = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float)
 
@@ -149,6 +155,9 @@ _SIGS = {
     "orbfe_kfdb_size": (_c_int, [_vp]),
     "orbfe_kfdb_shared_words": (_c_int, [_vp, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp, _vp]),
     "orbfe_kfdb_detect_reloc": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, KF_INFO_FN, _vp, _vp, _c_int, _vp]),
+    "orbfe_vocabulary_transform_batch": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
+    "orbfe_frame_compute_bow": (_c_int, [_vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "orbfe_kfdb_add_batch": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _vp]),
 }
 
 _lib = None

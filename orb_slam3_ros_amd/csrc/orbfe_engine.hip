@@ -1525,3 +1525,6 @@ int orbfe_descriptor_distance(const uint8_t* a, const uint8_t* b) {
 
 // KeyFrameDatabase for relocalisation: BowVectors resident in HBM, DetectRelocalizationCandidates.
 #include "orbfe_kfdb.hip"
+
+// Batched ComputeBoW on device-resident frames, and its path into the keyframe database.
+#include "orbfe_bow_batch.hip"

@@ -24,6 +24,15 @@ from . import _lib
 from .extractor import KEYPOINT_DTYPE
 
 
+def _compute_bow(fe, voc, levelsup, stream):
+    """ORBVocabulary.transform_batch over a front end's bound batch outputs (desc, counts)."""
+    from .vocabulary import BowBatch
+    bows = getattr(fe, "_bows", None)
+    if bows is None or (bows.nimg, bows.cap) != (int(fe.desc.shape[0]), fe.cap):
+        bows = fe._bows = BowBatch(int(fe.desc.shape[0]), fe.cap, fe.device)
+    return voc.transform_batch(fe.desc, fe.counts, levelsup, out=bows, stream=stream)
+
+
 class StereoFrontEnd:
     """`pipelines` > 1 splits the frames into that many sub-batches, each with its own engine handle
     and HIP stream, so the kernels of different sub-batches overlap on the GPU (the latency-bound
@@ -188,6 +197,12 @@ class StereoFrontEnd:
         kp = self.kps[i, :n].cpu().numpy().view(KEYPOINT_DTYPE).reshape(n)
         return mono, kp, self.desc[i, :n].cpu().numpy()
 
+    def compute_bow(self, voc, levelsup: int = 4, stream=None):
+        """Frame::ComputeBoW for all 2F images of the last run(), enqueued on the caller's current
+        torch stream (which run() ordered after its own) or on `stream` (a hipStream_t: the one run()
+        was given). No host wait. -> vocabulary.BowBatch, allocated once and filled again by later calls."""
+        return _compute_bow(self, voc, levelsup, stream)
+
     def host_frame(self, f: int):
         """(kps_left structured, desc_left, uright, depth) of frame f, copied to the host."""
         _, kp, d = self.host_image(2 * f)
@@ -254,6 +269,11 @@ class RGBDFrontEnd:
                                                     self.keys_un.data_ptr(), self.uright.data_ptr(),
                                                     self.depth.data_ptr(), s), "rgbd_stereo_batch")
         return self.uright, self.depth, self.keys_un
+
+    def compute_bow(self, voc, levelsup: int = 4, stream=None):
+        """Frame::ComputeBoW for all F images of the last run(), on the caller's current torch stream
+        (run()'s) or on `stream`. No host wait. -> vocabulary.BowBatch, allocated once and reused."""
+        return _compute_bow(self, voc, levelsup, stream)
 
     def host_frame(self, f: int):
         """(mvKeys, mvKeysUn, mDescriptors, mvuRight, mvDepth) of frame f, copied to the host."""

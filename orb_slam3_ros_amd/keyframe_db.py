@@ -44,6 +44,23 @@ class KeyFrameDatabase:
         _lib.check(self._lib.orbfe_kfdb_add(self._h, int(kf_id), ids.ctypes.data, w.ctypes.data, len(ids)),
                    "KeyFrameDatabase.add")
 
+    def add_batch(self, kf_ids, bow_batch, stream=None) -> None:
+        """add() for the images of a vocabulary.BowBatch, device to device: image i becomes keyframe
+        kf_ids[i] in array order, an id < 0 skips its image. The batch's vocabulary (the one whose
+        transform_batch filled it) must have this database's word count. stream: the hipStream_t the
+        batch was made on (default: the current torch stream); it is waited for. Refused as a whole
+        (nothing added) when an id repeats or is present, or an image to add has counts (-1, -1)."""
+        ids = np.ascontiguousarray(kf_ids, np.int32).reshape(-1)
+        if len(ids) != bow_batch.nimg:
+            raise ValueError("add_batch needs one keyframe id per image of the batch")
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(bow_batch.counts.device).cuda_stream
+        if bow_batch.voc is None:
+            raise ValueError("the batch has not been filled by ORBVocabulary.transform_batch")
+        _lib.check(self._lib.orbfe_kfdb_add_batch(self._h, bow_batch.voc._h, ids.ctypes.data, bow_batch.ref(), len(ids),
+                                                  bow_batch.cap, stream), "KeyFrameDatabase.add_batch")
+
     def erase(self, kf_id: int) -> None:
         _lib.check(self._lib.orbfe_kfdb_erase(self._h, int(kf_id)), "KeyFrameDatabase.erase")
 

@@ -7,6 +7,7 @@
 #pragma once
 #include <cstdint>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "orbfe.h"
@@ -174,6 +175,36 @@ inline int local_points(const orbfe_frame* F, const orbfe_camera* cam, const orb
     track.resize((size_t)n);
     return orbfe_search_local_points_track(F, cam, rig, pts, n, mvp, obs, th, bFarPoints ? 1 : 0, thFarPoints, 0.8f,
                                            n_to_match, track.data());
+}
+
+// Frame::ComputeBoW / KeyFrame::ComputeBoW (Frame.cc, KeyFrame.cc: mpORBvocabulary->transform(
+// vCurrentDesc, mBowVec, mFeatVec, 4)) as ONE orbfe_frame_compute_bow call: F is the frame's host view
+// or, while the extractor still holds the frame, its device view (on_current_frame below), whose
+// descriptors are then read in HBM.
+//   BowMap : DBoW2::BowVector      (std::map<WordId, WordValue>: unsigned -> double);
+//   FvMap  : DBoW2::FeatureVector  (std::map<NodeId, std::vector<unsigned>>).
+// Both are cleared and filled in ascending key order (hinted inserts at the end). Returns ORBFE_OK or
+// a library status with both maps empty; the caller then runs the reference's body.
+template <class BowMap, class FvMap>
+int compute_bow(const orbfe_vocabulary* voc, const orbfe_frame* F, int levelsup, BowMap& bow_map, FvMap& fv_map) {
+    bow_map.clear();
+    fv_map.clear();
+    if (!voc || !F || F->n < 0) return ORBFE_E_ARG;
+    const size_t n = (size_t)F->n;
+    std::vector<uint32_t> bid(n + 1), fid(n + 1), fidx(n + 1);
+    std::vector<double> bw(n + 1);
+    std::vector<int32_t> foff(n + 1);
+    int32_t nb = 0, nf = 0;
+    const int rc = orbfe_frame_compute_bow(voc, F, levelsup, bid.data(), bw.data(), &nb, fid.data(), foff.data(),
+                                           fidx.data(), &nf);
+    if (rc != ORBFE_OK) return rc;
+    for (int32_t i = 0; i < nb; i++)
+        bow_map.insert(bow_map.end(), typename BowMap::value_type(bid[(size_t)i], bw[(size_t)i]));
+    for (int32_t i = 0; i < nf; i++) {
+        typename FvMap::mapped_type idx(fidx.begin() + foff[(size_t)i], fidx.begin() + foff[(size_t)i + 1]);
+        fv_map.insert(fv_map.end(), typename FvMap::value_type(fid[(size_t)i], std::move(idx)));
+    }
+    return ORBFE_OK;
 }
 
 // Tracking's searches on the CURRENT frame read it in HBM when the extractor still holds it: call(F)
