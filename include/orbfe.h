@@ -396,7 +396,8 @@ int orbfe_search_by_bow(const orbfe_keypoint* kf_keys, const uint8_t* kf_desc, c
  * KF->device == 1 (a view of orbfe_frame_device_view) is copied device to device; KF->device == 0 is
  * host memory; fv is always host memory and is validated as orbfe_search_by_bow validates it
  * (offsets start at 0 and do not decrease, node ids strictly ascend, every index < n), else
- * ORBFE_E_ARG. The handle belongs to the HIP device current at create (using it with another device
+ * ORBFE_E_ARG. A keyframe with an empty FeatureVector keeps its angles and descriptors all the same
+ * (orbfe_search_by_projection_kf_batch reads the angles). The handle belongs to the HIP device current at create (using it with another device
  * current returns ORBFE_E_ARG), is immutable and may be used from any thread at once.
  * orbfe_keyframe_destroy(NULL) is a no-op; destroy must not race a call that uses the handle (the
  * caller orders them, as it orders KeyFrame deletion). create and destroy may wait for the device. */
@@ -637,6 +638,46 @@ typedef struct orbfe_kf_camera {
     float fx, fy, cx, cy;
     float log_scale_factor;          /* mfLogScaleFactor */
 } orbfe_kf_camera;
+
+/* SearchByProjection(CurrentFrame, kfs[c], sFound_c, th, ORBdist) (ORBmatcher.cc:1889-2010) for the
+ * surviving candidates of one sweep of Tracking::Relocalization's loop (Tracking.cc:3765: th 10, ORBdist
+ * 100; :3779: th 3, ORBdist 64) in one call and one kernel launch, one workgroup per candidate, with the
+ * projection on the device. Within a sweep the candidates are independent: each has its own pose, its own
+ * sFound and its own copy of mvpMapPoints.
+ * cur: a host view or a device view (orbfe_frame_device_view; read in HBM), single camera; a host view is
+ * uploaded once for all candidates. kfs[c]: the candidate's resident keyframe, NULL = candidate skipped.
+ * cams[c]: CurrentFrame's pose FOR CANDIDATE c: Tcw (an SE3), Ow = Tcw.inverse().translation() as the
+ * caller computed it, fx fy cx cy and log_scale_factor = CurrentFrame.mfLogScaleFactor. model:
+ * CurrentFrame.mpCamera (pinhole or KannalaBrandt8); NULL = pinhole from cams[c].
+ * pts[c]: [n_pts[c]] the keyframe's map points that are non-NULL, not bad and not in sFound_c, in
+ * ascending KF slot order (the reference loop's order: it decides who takes a keypoint first); read per
+ * point: pos, min_dist / max_dist (mfMinDistance / mfMaxDistance raw: the gates are 0.8f * min_dist and
+ * 1.2f * max_dist), id, desc. kf_idx[c][j]: the KF slot of point j, strictly ascending and
+ * < orbfe_keyframe_n(kfs[c]); it selects pKF->mvKeysUn[i].angle from the resident angles.
+ * Per point, in the reference's float order without contraction: x3Dc = Tcw * pos (Sophus), uv =
+ * project(x3Dc), the image bounds of cur, dist3D = |pos - Ow|, the distance gates, PredictScale
+ * (MapPoint.cc:531-546, glibc logf), radius = th * scale_factors[level], levels [level - 1, level + 1].
+ * As in the reference there is NO z > 0 test: a point behind the camera whose projection lands inside
+ * the bounds is searched. The one deliberate narrowing: a point whose uv is not finite is skipped (the
+ * reference would cast NaN to a grid cell).
+ * mvp: [n_kfs][cur->n] rows of CurrentFrame.mvpMapPoints handles, one per candidate, updated in place;
+ * nmatches: [n_kfs]. The search is orbfe_search_by_projection_kf's: a slot already holding a handle in
+ * row c is skipped, the smallest distance wins if <= ORBdist, points take slots in order, the rotation
+ * histogram clears the bins ComputeThreeMaxima drops. Row c and nmatches[c] are bit-identical to
+ * orbfe_search_by_projection_kf on row c with the records this projection defines; rows never affect
+ * each other. kfs[c] == NULL or n_pts[c] == 0 leaves row c untouched and sets nmatches[c] = 0. The
+ * results are complete on return. n_kfs == 0 returns ORBFE_OK.
+ * ORBFE_E_ARG: n_kfs < 0, a NULL cur / kfs / cams / pts / kf_idx / n_pts / mvp / nmatches, a NULL pts[c]
+ * or kf_idx[c] of a live candidate, n_pts[c] < 0, a kf_idx that is not strictly ascending inside the
+ * keyframe, a bad model type, cur->two_cams != 0, a keyframe handle of another device. ORBFE_E_CAPACITY:
+ * cur->n > 2048, an n_pts[c] > 2048, or a frame whose bounds do not fit the one-workgroup index. Every
+ * refusal comes before any device work and before any write to mvp or nmatches; the caller then searches
+ * per candidate (orbfe_search_by_projection_kf). Returns ORBFE_OK or a negative code. */
+int orbfe_search_by_projection_kf_batch(const orbfe_frame* cur, const orbfe_keyframe* const* kfs,
+                                        const orbfe_kf_camera* cams, const orbfe_camera_model* model,
+                                        const orbfe_map_point_3d* const* pts, const int32_t* const* kf_idx,
+                                        const int32_t* n_pts, int32_t n_kfs, int32_t* mvp, int32_t* nmatches,
+                                        float th, int32_t ORBdist, int32_t checkOri);
 
 /* A last-frame point for the device-projected motion-model search (ORBmatcher.cc:1695-1712): the
  * MapPoint's world position, nLastOctave and the keypoint angle of LastFrame (mvKeys / mvKeysRight),

@@ -158,6 +158,8 @@ _SIGS = {
     "orbfe_vocabulary_transform_batch": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
     "orbfe_frame_compute_bow": (_c_int, [_vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "orbfe_kfdb_add_batch": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _vp]),
+    "orbfe_search_by_projection_kf_batch": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _vp, _vp, _c_float,
+                                                     _c_int, _c_int]),
 }
 
 _lib = None

@@ -1136,11 +1136,16 @@ __device__ __forceinline__ int blk_list(const BlkQuery& Q, const BlkGeom& gm, co
                                    (uint32_t)((K[k] >> 40) << 16);
     return c;
 }
-template <int MODE>
-__global__ __launch_bounds__(MT_BLK_NT) void k_sbp_block(FrameDev fr, BlkGeom gm, const void* recs, int nq, float th,
-                                                         int a0, int a1, float thFar, float nnratio, int maxDist,
-                                                         int need_obs, BlkIO io) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t mt_sm[];
+// The one-workgroup search from the staged queries on: frame staging, candidate lists, the fixed point
+// and the commit, shared by k_sbp_block (records) and k_sbp_kf_batch (points projected in registers).
+// QS / qid / qang: the thread's queries q = tid + i * MT_BLK_NT (ok = false beyond nq), their handles and
+// query-side angles; reload(q): query q again, for a list that ran out. Ends after the slot writes with
+// every wave's stores complete and a barrier; returns the pass count, cnt = {assigned, dropped} (LDS).
+template <int MODE, typename Reload>
+__device__ __forceinline__ int blk_search(const FrameDev& fr, const BlkGeom& gm, const BlkQuery (&QS)[MT_BLK_QPT],
+                                          const int (&qid)[MT_BLK_QPT], const float (&qang)[MT_BLK_QPT], int nq,
+                                          float nnratio, int maxDist, int need_obs, const BlkIO& io, uint8_t* mt_sm,
+                                          Reload&& reload, const int*& cnt_out) {
     const int n = fr.n;
     const int nlev = fr.nlevels;
     const int nbk = nlev * gm.NB * gm.NS;
@@ -1159,34 +1164,16 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_block(FrameDev fr, BlkGeom gm
     // that earlier queries hold (first[idx] < q). A query whose list runs out while more candidates
     // exist re-enumerates its window with the pass's gates (exact, rare).
     uint32_t L[MT_BLK_QPT][MT_BLK_LIST];
-    int cnt[MT_BLK_QPT], obs[MT_BLK_QPT], res[MT_BLK_QPT], qid[MT_BLK_QPT];
-    float qang[MT_BLK_QPT];
+    int cnt[MT_BLK_QPT], obs[MT_BLK_QPT], res[MT_BLK_QPT];
     unsigned long long npair = 0;
-    // every record of the thread read first, before the frame is staged (the two memory round trips
-    // overlap: from host memory they are ~7 us each), with the fields the commit needs
-    BlkQuery QS[MT_BLK_QPT];
-#pragma unroll
-    for (int i = 0; i < MT_BLK_QPT; i++) {
-        cnt[i] = 0;
-        res[i] = -1;
-        qid[i] = -1;
-        qang[i] = 0.f;
-        QS[i].ok = false;
-        QS[i].obs = 0;
-        const int q = tid + i * MT_BLK_NT;
-        if (q >= nq) continue;
-        const uint8_t* rec = (const uint8_t*)recs + (size_t)q * io.q_stride;
-        qid[i] = *(const int*)(rec + io.qid_off);
-        if (io.checkOri) qang[i] = *(const float*)(rec + io.qangle_off);
-        QS[i] = blk_load<MODE>(fr, recs, q, th, a0, a1, thFar);
-    }
     if (tid < MT_HISTO) s_hist[tid] = 0;
     if (tid < 2) s_cnt[tid] = 0;
-    const void* rq = blk_qcopy(io, recs, nq);
     blk_stage<MT_BLK_NT>(fr, gm, io.mvp_in, io.obs_in, s_kp, s_desc, s_ber, s_blk, s_ang, s_first, s_ws);
 #pragma unroll
     for (int i = 0; i < MT_BLK_QPT; i++) {
         const int q = tid + i * MT_BLK_NT;
+        cnt[i] = 0;
+        res[i] = -1;
         obs[i] = QS[i].obs;
 #pragma unroll
         for (int k = 0; k < MT_BLK_LIST; k++) L[i][k] = 0xFFFFFFFFu;
@@ -1225,7 +1212,7 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_block(FrameDev fr, BlkGeom gm
             int result;
             if (found < (MODE == 0 ? 2 : 1) && cnt[i] > MT_BLK_LIST) {
                 // the list ran out: the window again, with this pass's gates
-                const BlkQuery Q = blk_load<MODE>(fr, rq, q, th, a0, a1, thFar);
+                const BlkQuery Q = reload(q);
                 unsigned long long k1 = ~0ull, k2 = ~0ull;
                 blk_enum<MODE>(Q, gm, s_kp, s_desc, s_be, s_blk, [&](unsigned long long key, int idx) {
                     if (fcur[idx] < q) return;
@@ -1315,14 +1302,45 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_block(FrameDev fr, BlkGeom gm
     // L2 sixteen times and cost more than the search
     __builtin_amdgcn_s_waitcnt(0);
     SYNC();
+    cnt_out = s_cnt;
+    return pass + 1;
+}
+template <int MODE>
+__global__ __launch_bounds__(MT_BLK_NT) void k_sbp_block(FrameDev fr, BlkGeom gm, const void* recs, int nq, float th,
+                                                         int a0, int a1, float thFar, float nnratio, int maxDist,
+                                                         int need_obs, BlkIO io) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t mt_sm[];
+    const int tid = threadIdx.x;
+    int qid[MT_BLK_QPT];
+    float qang[MT_BLK_QPT];
+    // every record of the thread read first, before the frame is staged (the two memory round trips
+    // overlap: from host memory they are ~7 us each), with the fields the commit needs
+    BlkQuery QS[MT_BLK_QPT];
+#pragma unroll
+    for (int i = 0; i < MT_BLK_QPT; i++) {
+        qid[i] = -1;
+        qang[i] = 0.f;
+        QS[i].ok = false;
+        QS[i].obs = 0;
+        const int q = tid + i * MT_BLK_NT;
+        if (q >= nq) continue;
+        const uint8_t* rec = (const uint8_t*)recs + (size_t)q * io.q_stride;
+        qid[i] = *(const int*)(rec + io.qid_off);
+        if (io.checkOri) qang[i] = *(const float*)(rec + io.qangle_off);
+        QS[i] = blk_load<MODE>(fr, recs, q, th, a0, a1, thFar);
+    }
+    const void* rq = blk_qcopy(io, recs, nq);
+    const int* cnt;
+    const int passes = blk_search<MODE>(fr, gm, QS, qid, qang, nq, nnratio, maxDist, need_obs, io, mt_sm,
+                                        [&](int q) { return blk_load<MODE>(fr, rq, q, th, a0, a1, thFar); }, cnt);
     if (tid == 0) {
         __threadfence_system();
-        if (io.stats) io.stats[2] = (unsigned long long)(pass + 1);
+        if (io.stats) io.stats[2] = (unsigned long long)passes;
         volatile int* st = io.st_host;
         st[0] = 0;
-        st[1] = s_cnt[0];
-        st[2] = s_cnt[1];
-        st[3] = pass + 1;
+        st[1] = cnt[0];
+        st[2] = cnt[1];
+        st[3] = passes;
         st[5] = io.ntm ? *io.ntm : 0;
         __threadfence_system();
         st[4] = io.seq;
@@ -2514,6 +2532,126 @@ __host__ __device__ __forceinline__ unsigned mt_three_maxima_keep(const int* his
     if (ind2 >= 0) keep |= 1u << ind2;
     if (ind3 >= 0) keep |= 1u << ind3;
     return keep;
+}
+
+// ---- SearchByProjection(CurrentFrame, pKF, sFound, th, ORBdist) (ORBmatcher.cc:1889-2010) for the
+// surviving candidates of one Tracking::Relocalization sweep (Tracking.cc:3765 / :3779) in ONE launch:
+// workgroup c = candidate c, k_sbp_block<2>'s search (blk_search) with the queries made here, in
+// registers, from the candidate's map points (it stands after the projection pieces it composes).
+// Candidate c: CurrentFrame's pose for it (Sophus Tcw, the caller's Ow), the camera model, its points
+// (world position, distance limits, handle, descriptor) and their KF slots, which address the resident
+// keypoint angles (pKF->mvKeysUn[i].angle). nq == 0: a skipped candidate. o_pts / o_idx: where the
+// call's upload put the points and slots, from KfbIn::arena.
+struct KfbCand {
+    size_t o_pts, o_idx;
+    const float* ang;
+    int nq;
+    float logsf;
+    orbfe_pose T;
+    float Ow[3];
+    CamModelDev cam;
+};
+// Point p as a query (ORBmatcher.cc:1911-1939): x3Dc = Tcw * x3Dw, uv = mpCamera->project(x3Dc), the
+// image bounds, dist3D = |x3Dw - Ow| inside [0.8 mfMinDistance, 1.2 mfMaxDistance], PredictScale
+// (MapPoint.cc:531-546), radius = th * mvScaleFactors[level], levels [level - 1, level + 1]. No z > 0
+// test: the reference has none here. A non-finite uv is skipped (the reference would cast NaN to a cell).
+__device__ __forceinline__ BlkQuery kfb_query(const FrameDev& fr, const KfbCand& cd, const orbfe_map_point_3d& p,
+                                              float th) {
+    BlkQuery Q;
+    Q.x = Q.y = Q.R = Q.xr = 0.f;
+    Q.olo = 0;
+    Q.ohi = -1;
+    Q.obs = 0;
+    Q.ok = false;
+    const float pos[3] = {p.pos[0], p.pos[1], p.pos[2]};
+    float c[3];
+    be_pose_apply(cd.T, pos, c);
+    const float2 uv = mt_cam_project(cd.cam, c[0], c[1], c[2]);
+    if (!(fabsf(uv.x) < INFINITY && fabsf(uv.y) < INFINITY)) return Q;
+    if (uv.x < fr.minx || uv.x > fr.maxx) return Q;
+    if (uv.y < fr.miny || uv.y > fr.maxy) return Q;
+    const float PO0 = pos[0] - cd.Ow[0], PO1 = pos[1] - cd.Ow[1], PO2 = pos[2] - cd.Ow[2];
+    const float dist3D = sqrtf(eig_sum3(PO0 * PO0, PO1 * PO1, PO2 * PO2));
+    const float maxDistance = 1.2f * p.max_dist, minDistance = 0.8f * p.min_dist;
+    if (dist3D < minDistance || dist3D > maxDistance) return Q;
+    const float ratio = p.max_dist / dist3D;
+    int lvl = (int)ceilf(glibc_logf(ratio) / cd.logsf);
+    if (lvl < 0) lvl = 0;
+    else if (lvl >= fr.nlevels) lvl = fr.nlevels - 1;
+    Q.ok = true;
+    Q.R = th * fr.scale[lvl];
+    Q.x = uv.x;
+    Q.y = uv.y;
+    Q.olo = max(lvl - 1, 0);   // GetFeaturesInArea(.., level - 1, level + 1): bCheckLevels always holds
+    Q.ohi = min(lvl + 1, fr.nlevels - 1);
+    memcpy(Q.qd, p.desc, 32);
+    return Q;
+}
+// mvp_in / mvp_out: [n_kfs][fr.n] rows (device copy in, mapped pinned out: a row's untouched slots keep
+// the value the host put there). counts: [n_kfs][2] = {assigned, dropped} per candidate, mapped pinned.
+// done: zeroed by the call's upload; the workgroup that brings it to gridDim.x has seen every other
+// one's release, and publishes the sequence word as k_sbp_block's tail does.
+struct KfbIn {
+    const KfbCand* cands;
+    const uint8_t* arena;
+    const int32_t* mvp_in;
+    int32_t* mvp_out;
+    int* counts;
+    int* done;
+    int* st_host;
+    int seq, checkOri, maxDist;
+    float th;
+};
+__global__ __launch_bounds__(MT_BLK_NT) void k_sbp_kf_batch(FrameDev fr, BlkGeom gm, KfbIn in) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t mt_sm[];
+    const int tid = threadIdx.x, c = blockIdx.x;
+    const KfbCand& cd = in.cands[c];
+    const int nq = cd.nq;
+    const int* cnt = nullptr;
+    if (nq > 0) {   // (uniform over the workgroup)
+        const orbfe_map_point_3d* pts = (const orbfe_map_point_3d*)(in.arena + cd.o_pts);
+        const int32_t* kf_idx = (const int32_t*)(in.arena + cd.o_idx);
+        int qid[MT_BLK_QPT];
+        float qang[MT_BLK_QPT];
+        BlkQuery QS[MT_BLK_QPT];
+#pragma unroll
+        for (int i = 0; i < MT_BLK_QPT; i++) {
+            qid[i] = -1;
+            qang[i] = 0.f;
+            QS[i].ok = false;
+            QS[i].obs = 0;
+            const int q = tid + i * MT_BLK_NT;
+            if (q >= nq) continue;
+            qid[i] = pts[q].id;
+            if (in.checkOri) qang[i] = cd.ang[kf_idx[q]];
+            QS[i] = kfb_query(fr, cd, pts[q], in.th);
+        }
+        const size_t row = (size_t)c * fr.n;
+        const BlkIO io{in.mvp_in + row, nullptr, in.mvp_out + row, 0, 0, 0, in.checkOri, nullptr, nullptr, 0, nullptr,
+                       nullptr};
+        blk_search<2>(fr, gm, QS, qid, qang, nq, 0.f, in.maxDist, 0, io, mt_sm,
+                      [&](int q) { return kfb_query(fr, cd, pts[q], in.th); }, cnt);
+    }
+    if (tid == 0) {
+        volatile int* co = in.counts + 2 * c;
+        co[0] = cnt ? cnt[0] : 0;
+        co[1] = cnt ? cnt[1] : 0;
+        // this workgroup's rows and counts are released at system scope before it is counted
+        __threadfence_system();
+        const int before = __hip_atomic_fetch_add(in.done, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (before == (int)gridDim.x - 1) {
+            __threadfence_system();
+            volatile int* st = in.st_host;
+            st[0] = 0;
+            st[1] = (int)gridDim.x;
+            st[2] = 0;
+            st[3] = 0;
+            st[5] = 0;
+            __threadfence_system();
+            st[4] = in.seq;
+            __threadfence_system();
+        }
+    }
 }
 
 // Final write-back for slot-assigning searches: slot k gets the LAST query that chose it; with
@@ -4525,7 +4663,8 @@ int sbp_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs
 struct orbfe_keyframe {
     int device = -1;
     int n = 0, nn = 0;
-    uint8_t* pack = nullptr;
+    uint8_t* pack = nullptr;   // n > 0
+    bool bow = false;          // the pack holds a FeatureVector with indices (else SearchByBoW's row is empty)
     int nvec = 0;
     int o_off = 0, o_idx = 0, o_ang = 0, o_desc = 0;
     std::vector<uint32_t> node_ids;
@@ -4584,6 +4723,109 @@ int orbfe_search_by_projection_lastframe(const orbfe_frame* cur, int32_t* mvp, c
 int orbfe_search_by_projection_kf(const orbfe_frame* cur, int32_t* mvp, const orbfe_proj_point* pts, int32_t n_pts,
                                   float th, int32_t ORBdist, int32_t checkOri) {
     return sbp_run(2, cur, mvp, nullptr, pts, n_pts, kProjPointRec, th, 0, 0, 0.f, 0.f, ORBdist, checkOri);
+}
+
+int orbfe_search_by_projection_kf_batch(const orbfe_frame* cur, const orbfe_keyframe* const* kfs,
+                                        const orbfe_kf_camera* cams, const orbfe_camera_model* model,
+                                        const orbfe_map_point_3d* const* pts, const int32_t* const* kf_idx,
+                                        const int32_t* n_pts, int32_t n_kfs, int32_t* mvp, int32_t* nmatches, float th,
+                                        int32_t ORBdist, int32_t checkOri) {
+    // every refusal below comes before any device work and before any write to mvp / nmatches
+    if (n_kfs < 0) return ORBFE_E_ARG;
+    if (n_kfs == 0) return ORBFE_OK;
+    if (!cur || !kfs || !cams || !pts || !kf_idx || !n_pts || !mvp || !nmatches) return ORBFE_E_ARG;
+    orbfe_frame Fchk = *cur;
+    Fchk.device = 0;   // a device view's arrays are checked for presence only
+    if (!frame_ok(&Fchk) || cur->two_cams) return ORBFE_E_ARG;
+    if (model && model->type != ORBFE_CAM_PINHOLE && model->type != ORBFE_CAM_KANNALA_BRANDT8) return ORBFE_E_ARG;
+    const int n = cur->n;
+    bool any = false;
+    for (int c = 0; c < n_kfs; c++) {
+        if (n_pts[c] < 0) return ORBFE_E_ARG;
+        if (!kfs[c] || n_pts[c] == 0) continue;
+        if (!pts[c] || !kf_idx[c]) return ORBFE_E_ARG;
+        any = true;
+    }
+    if (n > MT_BAND_MAXN) return ORBFE_E_CAPACITY;
+    for (int c = 0; c < n_kfs; c++)
+        if (n_pts[c] > MT_BLOCK_MAXQ) return ORBFE_E_CAPACITY;
+    BlkGeom gm;
+    if (n > 0 && !blk_geom(cur, gm)) return ORBFE_E_CAPACITY;
+    if ((size_t)n_kfs * (size_t)std::max(n, 1) > ((size_t)1 << 26)) return ORBFE_E_CAPACITY;
+    for (int c = 0; c < n_kfs; c++) {   // KF slots: strictly ascending, inside the keyframe
+        if (!kfs[c]) continue;
+        int prev = -1;
+        for (int j = 0; j < n_pts[c]; j++) {
+            const int k = kf_idx[c][j];
+            if (k <= prev || k >= kfs[c]->n) return ORBFE_E_ARG;
+            prev = k;
+        }
+    }
+    if (any && n > 0) {   // a handle belongs to its create's device
+        int dev = 0;
+        HIPCHK(hipGetDevice(&dev));
+        for (int c = 0; c < n_kfs; c++)
+            if (kfs[c] && n_pts[c] > 0 && (kfs[c]->device != dev || !kfs[c]->pack)) return ORBFE_E_ARG;
+    }
+    for (int c = 0; c < n_kfs; c++) nmatches[c] = 0;
+    if (!any || n == 0) return ORBFE_OK;
+    // one upload for the call: the frame (unless a device view), every candidate's points and KF
+    // slots, the rows, the candidate table and the zeroed completion counter
+    Plan p;
+    FramePlan fp;
+    if (cur->device) fp.plan_dev(cur, false);
+    else fp.plan(p, cur, true, false);
+    std::vector<size_t> o_pts(n_kfs, 0), o_idx(n_kfs, 0);
+    for (int c = 0; c < n_kfs; c++) {
+        if (!kfs[c] || n_pts[c] == 0) continue;
+        o_pts[c] = p.upload(pts[c], (size_t)n_pts[c] * sizeof(orbfe_map_point_3d));
+        o_idx[c] = p.upload(kf_idx[c], (size_t)n_pts[c] * 4);
+    }
+    const size_t o_mvp = p.upload(mvp, (size_t)n_kfs * n * 4);
+    std::vector<KfbCand> cands(n_kfs);
+    const size_t o_cands = p.upload(cands.data(), (size_t)n_kfs * sizeof(KfbCand));   // filled below, copied by ms_prepare
+    const int zero = 0;
+    const size_t o_done = p.upload(&zero, 4);
+    for (int c = 0; c < n_kfs; c++) {
+        KfbCand& cd = cands[c];
+        memset(&cd, 0, sizeof(cd));
+        if (!kfs[c] || n_pts[c] == 0) continue;
+        cd.nq = n_pts[c];
+        cd.o_pts = o_pts[c];
+        cd.o_idx = o_idx[c];
+        cd.ang = (const float*)(kfs[c]->pack + kfs[c]->o_ang);
+        cd.logsf = cams[c].log_scale_factor;
+        cd.T = cams[c].Tcw;
+        cd.T.kind = ORBFE_SE3;
+        memcpy(cd.Ow, cams[c].Ow, sizeof(cd.Ow));
+        cd.cam.type = model ? model->type : ORBFE_CAM_PINHOLE;
+        cd.cam.fx = model ? model->params[0] : cams[c].fx;
+        cd.cam.fy = model ? model->params[1] : cams[c].fy;
+        cd.cam.cx = model ? model->params[2] : cams[c].cx;
+        cd.cam.cy = model ? model->params[3] : cams[c].cy;
+        for (int k = 0; k < 4; k++)
+            cd.cam.k[k] = (model && model->type == ORBFE_CAM_KANNALA_BRANDT8) ? model->params[4 + k] : 0.f;
+    }
+    MSCHK(ms_prepare(p));
+    const size_t nrow = (size_t)n_kfs * n, nout = nrow + 2 * (size_t)n_kfs;   // the rows, then {assigned, dropped}
+    MSCHK(ms_out_block(nout, std::max<size_t>(nout + nout / 2, 2048)));
+    MatchScratch& m = t_ms;
+    hipStream_t s = m.stream;
+    MsTimer timer(s);
+    const FrameDev fr = fp.view();
+    const int seq = ++t_ms.seq;
+    memcpy(m.ho, mvp, nrow * 4);   // the slots the search leaves alone keep their value
+    const KfbIn in{ms_ptr<const KfbCand>(o_cands), ms_ptr<const uint8_t>(0), ms_ptr<const int32_t>(o_mvp), m.ho_dev,
+                   m.ho_dev + nrow,
+                   ms_ptr<int>(o_done), t_ms.hs_dev, seq, checkOri ? 1 : 0, ORBdist, th};
+    // one workgroup per candidate, each with k_sbp_block's LDS frame
+    hipLaunchKernelGGL(k_sbp_kf_batch, dim3(n_kfs), dim3(MT_BLK_NT), blk_lds(n, cur->nlevels, gm), s, fr, gm, in);
+    HIPCHK(hipGetLastError());
+    timer.end();
+    MSCHK(ms_wait_seq(s, seq));
+    memcpy(mvp, m.ho, nrow * 4);   // complete: the sequence word comes after every workgroup's release
+    for (int c = 0; c < n_kfs; c++) nmatches[c] = m.ho[nrow + 2 * c] - m.ho[nrow + 2 * c + 1];
+    return ORBFE_OK;
 }
 
 static int sfi_core(const orbfe_frame* F1, const orbfe_frame* F2, float* prev_matched, int32_t* matches12,
@@ -4829,19 +5071,22 @@ int orbfe_keyframe_create(const orbfe_frame* KF, const orbfe_feature_vector* fv,
     kf->n = n;
     kf->nn = nn;
     if (nn > 0) kf->node_ids.assign(fv->node_ids, fv->node_ids + nn);
-    if (n == 0 || nki == 0) {   // nothing to match: no pack, every search gives the empty row
+    if (n == 0) {   // nothing to match: no pack, every search gives the empty row
         *out = kf.release();
         return ORBFE_OK;
     }
+    kf->bow = nki > 0;   // an empty FeatureVector: SearchByBoW's row is empty, the angles still serve SearchByProjection
     kf->nvec = (int)(total / 16);
     kf->o_off = (int)o_off;
     kf->o_idx = (int)o_idx;
     kf->o_ang = (int)o_ang;
     kf->o_desc = (int)o_desc;
     std::vector<uint8_t> h(o_desc, 0);
-    memcpy(h.data(), fv->node_ids, (size_t)nn * 4);
-    memcpy(h.data() + o_off, fv->offsets, (size_t)(nn + 1) * 4);
-    memcpy(h.data() + o_idx, fv->indices, (size_t)nki * 4);
+    if (nn > 0) {
+        memcpy(h.data(), fv->node_ids, (size_t)nn * 4);
+        memcpy(h.data() + o_off, fv->offsets, (size_t)(nn + 1) * 4);
+    }
+    if (nki > 0) memcpy(h.data() + o_idx, fv->indices, (size_t)nki * 4);
     if (!KF->device) {
         float* ang = (float*)(h.data() + o_ang);
         for (int i = 0; i < n; i++) ang[i] = KF->keys[i].angle;
@@ -4890,7 +5135,7 @@ int orbfe_search_by_bow_batch(const orbfe_keyframe* const* kfs, const int32_t* c
     for (int c = 0; c < n_kfs; c++) {
         nmatches[c] = 0;
         if (kfs[c] && kfs[c]->n > 0 && !kf_mp[c]) return ORBFE_E_ARG;
-        any = any || (kfs[c] && kfs[c]->pack);
+        any = any || (kfs[c] && kfs[c]->bow);
     }
     for (size_t i = 0; i < (size_t)n_kfs * fn; i++) out[i] = -1;
     if (fn == 0 || fnn == 0 || !any) return ORBFE_OK;
@@ -4937,7 +5182,7 @@ int orbfe_search_by_bow_batch(const orbfe_keyframe* const* kfs, const int32_t* c
         BowCand& cd = cands[c];
         memset(&cd, 0, sizeof(cd));
         cd.mode = 1;
-        if (!k || !k->pack) continue;
+        if (!k || !k->bow) continue;
         o_mp[c] = p.upload(kf_mp[c], (size_t)k->n * 4);
         cd = BowCand{(const uint4*)k->pack, k->nvec, k->o_off, k->o_idx, k->o_ang, k->o_desc, k->nn, k->n, 0, 0};
         const size_t need = bow_batch_lds(nvec_fm, fn, k->nvec, k->n) + 16;

@@ -379,6 +379,54 @@ class ORBmatcher:
             cur.ref(), mvp.ctypes.data, pts.ctypes.data, len(pts), float(th), int(ORBdist),
             int(self.mbCheckOrientation)), "SearchByProjection(keyframe)")
 
+    # the SearchByProjection(mCurrentFrame, vpCandidateKFs[i], sFound, th, ORBdist) calls of one sweep of
+    # Tracking::Relocalization's candidates loop (Tracking.cc:3765, :3779) in one call
+    def SearchByProjectionKeyFrameBatch(self, cur, kfs, cams, points, kf_idx, mvp, th: float, ORBdist: int,
+                                        model: "CameraModel" = None):
+        """kfs: KeyFrameFeatures or None (a skipped candidate) per candidate; cams[c]: KFCamera with the
+        current frame's pose for candidate c (Tcw, Ow, intrinsics, mfLogScaleFactor); points[c]:
+        MAP_POINT_3D_DTYPE records of the keyframe's map points that are not bad and not already found, in
+        ascending KF slot order; kf_idx[c]: int32 KF slot per point (strictly ascending); mvp: contiguous
+        int32 [C, cur.N], row c = the frame's slots for candidate c, updated in place. cur may be a
+        current_frame_view. The projection (ORBmatcher.cc:1904-1939) runs on the device. Returns nmatches
+        int32 [C]; row c equals SearchByProjectionKeyFrame on the projected records of candidate c.
+        Raises _lib.OrbfeCapacityError beyond 2048 keypoints or 2048 points per candidate (nothing is
+        written then: search per candidate)."""
+        C = len(kfs)
+        if not (len(cams) == len(points) == len(kf_idx) == C):
+            raise ValueError("one cams / points / kf_idx entry per candidate")
+        mvp = np.asarray(mvp)
+        if mvp.dtype != np.int32 or not mvp.flags.c_contiguous or mvp.shape != (C, cur.N):
+            raise ValueError(f"mvp must be a contiguous int32 array of shape ({C}, {cur.N})")
+        handles = (ctypes.c_void_p * max(C, 1))()
+        pp = (ctypes.c_void_p * max(C, 1))()
+        ip = (ctypes.c_void_p * max(C, 1))()
+        cam_arr = (KFCamera * max(C, 1))()
+        npts = np.zeros(max(C, 1), np.int32)
+        keep = []
+        for c, kf in enumerate(kfs):
+            if not isinstance(cams[c], KFCamera):
+                raise ValueError("cams must hold KFCamera structures")
+            cam_arr[c] = cams[c]
+            if kf is None:
+                continue
+            if kf.handle is None:
+                raise ValueError("KeyFrameFeatures is closed")
+            pts = _records(points[c], MAP_POINT_3D_DTYPE, "points")
+            idx = _i32(kf_idx[c], len(pts), "kf_idx")
+            keep += [pts, idx]
+            handles[c] = kf.handle
+            pp[c] = pts.ctypes.data if len(pts) else None
+            ip[c] = idx.ctypes.data if len(pts) else None
+            npts[c] = len(pts)
+        nm = np.zeros(C, np.int32)
+        if C:
+            _lib.check(self._lib.orbfe_search_by_projection_kf_batch(
+                cur.ref(), handles, cam_arr, ctypes.byref(model) if model is not None else None, pp, ip,
+                npts.ctypes.data, C, mvp.ctypes.data, nm.ctypes.data, float(th), int(ORBdist),
+                int(self.mbCheckOrientation)), "SearchByProjection(keyframe, batch)")
+        return nm
+
     def SearchByProjection(self, *args, **kw) -> int:
         """Overload dispatch like the C++ name: (F, mvp, mvp_obs, MAP_POINT records, ...) -> local map;
         (F, mvp, mvp_obs, PROJ_POINT records, th, bForward, bBackward) -> last frame;

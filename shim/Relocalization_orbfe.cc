@@ -13,11 +13,13 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
+#include <set>
 #include <unordered_map>
 
 #include <orbfe.h>
 
 #include "orbfe_glue.h"
+#include "orbfe_slam_types.h"
 
 #include "Frame.h"
 #include "KeyFrame.h"
@@ -198,6 +200,137 @@ void SearchByBoWCandidates(const vector<KeyFrame*>& vpCandidateKFs, Frame& F, fl
         vvpMapPointMatches[c].assign(F.N, nullptr);
         const int32_t* row = out.data() + c * (size_t)F.N;
         for (int i = 0; i < F.N; i++) vvpMapPointMatches[c][i] = row[i] < 0 ? nullptr : table[row[i]];
+    }
+}
+
+namespace {
+
+// Frame::SetPose (include/Frame.h). The stand-in Frame this repository compiles the shim against
+// (tests/shim_stubs/Frame.h) declares no SetPose: there the second overload is chosen and reports it.
+template <class Fr>
+auto set_pose(Fr& F, const Sophus::SE3f& Tcw, int) -> decltype(F.SetPose(Tcw), true) {
+    F.SetPose(Tcw);
+    return true;
+}
+template <class Fr>
+bool set_pose(Fr&, const Sophus::SE3f&, long) {
+    fprintf(stderr, "[orbfe] Frame has no SetPose: the per-candidate SearchByProjection cannot run\n");
+    return false;
+}
+
+// the reference calls, one candidate at a time: F takes the candidate's pose and slots for its call
+void sbp_per_candidate(Frame& F, const vector<KeyFrame*>& vpKFs, const vector<Sophus::SE3f>& vTcw,
+                       const vector<set<MapPoint*>>& vsFound, vector<vector<MapPoint*>>& vvp, float th, int ORBdist,
+                       bool checkOri, vector<int>& vn) {
+    ORBmatcher matcher(0.9, checkOri);
+    const Sophus::SE3f Tcw0 = F.GetPose();
+    const vector<MapPoint*> mvp0 = F.mvpMapPoints;
+    for (size_t c = 0; c < vpKFs.size(); c++) {
+        vn[c] = 0;
+        if (!vpKFs[c]) continue;
+        if (!set_pose(F, vTcw[c], 0)) break;
+        F.mvpMapPoints = vvp[c];
+        vn[c] = matcher.SearchByProjection(F, vpKFs[c], vsFound[c], th, ORBdist);
+        vvp[c] = F.mvpMapPoints;
+    }
+    set_pose(F, Tcw0, 0);
+    F.mvpMapPoints = mvp0;
+}
+
+}  // namespace
+
+void SearchByProjectionCandidates(Frame& F, const vector<KeyFrame*>& vpKFs, const vector<Sophus::SE3f>& vTcw,
+                                  const vector<set<MapPoint*>>& vsFound, vector<vector<MapPoint*>>& vvpMapPoints,
+                                  float th, int ORBdist, bool checkOri, vector<int>& vnAdditional) {
+    const size_t C = vpKFs.size();
+    vnAdditional.assign(C, 0);
+    if (C == 0) return;
+    auto fallback = [&] {
+        sbp_per_candidate(F, vpKFs, vTcw, vsFound, vvpMapPoints, th, ORBdist, checkOri, vnAdditional);
+    };
+    // two-camera frames are not batched (the call refuses them): straight to the per-candidate calls
+    if (F.Nleft != -1) return fallback();
+    // per candidate: the resident keyframe, CurrentFrame's pose for it, and the map points the reference
+    // loop would project (non-NULL, not bad, not in sFound; ORBmatcher.cc:1905-1911) in KF slot order
+    vector<const orbfe_keyframe*> kfs(C, nullptr);
+    vector<orbfe_kf_camera> cams(C);
+    vector<vector<orbfe_map_point_3d>> pts(C);
+    vector<vector<int32_t>> idx(C);
+    vector<const orbfe_map_point_3d*> pts_ptr(C, nullptr);
+    vector<const int32_t*> idx_ptr(C, nullptr);
+    vector<int32_t> npts(C, 0);
+    vector<MapPoint*> table;
+    unordered_map<MapPoint*, int32_t> id;
+    auto handle = [&](MapPoint* p) -> int32_t {
+        if (!p) return -1;
+        auto it = id.find(p);
+        if (it == id.end()) {
+            it = id.emplace(p, (int32_t)table.size()).first;
+            table.push_back(p);
+        }
+        return it->second;
+    };
+    memset(cams.data(), 0, C * sizeof(orbfe_kf_camera));
+    for (size_t c = 0; c < C; c++) {
+        KeyFrame* pKF = vpKFs[c];
+        if (!pKF) continue;
+        kfs[c] = cache().get(pKF);
+        const vector<MapPoint*> vp = pKF->GetMapPointMatches();
+        if (!kfs[c] || (int)vp.size() != orbfe_keyframe_n(kfs[c]) || (int)vvpMapPoints[c].size() != F.N) return fallback();
+        orbfe_kf_camera& cam = cams[c];
+        cam.Tcw = orbfe_shim::pose_of(vTcw[c]);
+        const Eigen::Vector3f Ow = vTcw[c].inverse().translation();   // ORBmatcher.cc:1894
+        cam.Ow[0] = Ow(0); cam.Ow[1] = Ow(1); cam.Ow[2] = Ow(2);
+        cam.log_scale_factor = F.mfLogScaleFactor;
+        for (size_t i = 0; i < vp.size(); i++) {
+            MapPoint* p = vp[i];
+            if (!p || p->isBad() || vsFound[c].count(p)) continue;
+            orbfe_map_point_3d r;
+            memset(&r, 0, sizeof(r));
+            const Eigen::Vector3f x3Dw = p->GetWorldPos();
+            r.pos[0] = x3Dw(0); r.pos[1] = x3Dw(1); r.pos[2] = x3Dw(2);
+            r.min_dist = p->GetMinDistance();   // accessors INTEGRATION.md §2 adds to MapPoint.h
+            r.max_dist = p->GetMaxDistance();
+            r.id = handle(p);
+            memcpy(r.desc, p->GetDescriptor().ptr<uint8_t>(0), 32);
+            pts[c].push_back(r);
+            idx[c].push_back((int32_t)i);
+        }
+        npts[c] = (int32_t)pts[c].size();
+        pts_ptr[c] = pts[c].data();
+        idx_ptr[c] = idx[c].data();
+    }
+    const orbfe_camera_model model = orbfe_shim::model_of(F.mpCamera);
+    vector<int32_t> mvp(C * (size_t)F.N, -1), nm(C, 0);
+    for (size_t c = 0; c < C; c++)
+        for (int i = 0; kfs[c] && i < F.N; i++) mvp[c * (size_t)F.N + i] = handle(vvpMapPoints[c][i]);
+    orbfe_frame fr;
+    memset(&fr, 0, sizeof(fr));
+    fr.n = F.N;
+    fr.keys = reinterpret_cast<const orbfe_keypoint*>(F.mvKeysUn.data());
+    fr.desc = F.mDescriptors.data;
+    fr.min_x = Frame::mnMinX; fr.max_x = Frame::mnMaxX; fr.min_y = Frame::mnMinY; fr.max_y = Frame::mnMaxY;
+    fr.nlevels = F.mnScaleLevels;
+    fr.scale_factors = F.mvScaleFactors.data();
+    fr.mbf = F.mbf;
+    orbfe_extractor* hl = F.mpORBextractorLeft ? static_cast<orbfe_extractor*>(F.mpORBextractorLeft->OrbfeHandle()) : nullptr;
+    const int rc = orbfe_glue::on_current_frame(hl, F.mnOrbfeFrameId, fr, [&](const orbfe_frame* V) {
+        return orbfe_search_by_projection_kf_batch(V, kfs.data(), cams.data(), &model, pts_ptr.data(), idx_ptr.data(),
+                                                   npts.data(), (int32_t)C, mvp.data(), nm.data(), th, ORBdist,
+                                                   checkOri ? 1 : 0);
+    });
+    if (rc < 0) {
+        static once_flag logged;
+        call_once(logged, [rc] {
+            fprintf(stderr, "[orbfe] orbfe_search_by_projection_kf_batch returned %d; searching per candidate\n", rc);
+        });
+        return fallback();
+    }
+    for (size_t c = 0; c < C; c++) {
+        if (!kfs[c]) continue;
+        vnAdditional[c] = nm[c];
+        const int32_t* row = mvp.data() + c * (size_t)F.N;
+        for (int i = 0; i < F.N; i++) vvpMapPoints[c][i] = row[i] < 0 ? nullptr : table[row[i]];
     }
 }
 
