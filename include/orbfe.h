@@ -954,6 +954,19 @@ enum {
     ORBFE_SBP_FORM_PROJ2 = 12     /* two cameras, last frame / keyframe, multi-launch */
 };
 int orbfe_matcher_last_form(void);
+/* The same for SearchByBoW. orbfe_matcher_last_bow_form: the form of this thread's last orbfe_search_by_bow,
+ * orbfe_search_by_bow_kf or orbfe_search_by_bow_kf2 call (ORBFE_BOW_FORM_NONE for a refused or empty one).
+ * orbfe_matcher_last_bow_batch: of this thread's last orbfe_search_by_bow_batch, how many candidates
+ * out[0] matched in k_bow_batch's one workgroup, out[1] got the empty row (NULL, no features, no shared
+ * node, or a call that returned before any launch), out[2] took k_bow_nodes + k_bow_commit_ang. */
+enum {
+    ORBFE_BOW_FORM_NONE = 0,
+    ORBFE_BOW_FORM_BLOCK = 1,   /* k_bow_block, one workgroup */
+    ORBFE_BOW_FORM_NODES = 2,   /* k_bow_nodes + k_bow_commit */
+    ORBFE_BOW_FORM_KFKF = 3     /* k_bow_kfkf + k_bow_kfkf_commit */
+};
+int orbfe_matcher_last_bow_form(void);
+int orbfe_matcher_last_bow_batch(int32_t* out);
 
 /* Debug/inspection (tests only): copy an intermediate of image `image`, level `level` of the last
  * batch to host memory. what: 0 = per-cell FAST key counts (int32[n_cells]),

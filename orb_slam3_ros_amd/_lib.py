@@ -117,6 +117,8 @@ _SIGS = {
     "orbfe_matcher_set_stats": (_c_int, [_c_int]),
     "orbfe_matcher_last_stats": (_c_int, [_vp]),
     "orbfe_matcher_last_form": (_c_int, []),
+    "orbfe_matcher_last_bow_form": (_c_int, []),
+    "orbfe_matcher_last_bow_batch": (_c_int, [_vp]),
     "orbfe_undistort_points": (_c_int, [_vp, _c_int, _vp, _vp, _c_int, _vp]),
     "orbfe_remap_linear": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _vp, _c_int]),
     "orbfe_remap_linear_batch": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _vp, _c_int, _c_int, _vp]),

@@ -405,6 +405,7 @@ int orbfe_search_by_bow_kf2(const orbfe_keypoint* keys1, const uint8_t* desc1, c
                             int32_t nleft1, const orbfe_feature_vector* fv1, const orbfe_keypoint* keys2,
                             const uint8_t* desc2, const int32_t* mp2, int32_t n2, int32_t nleft2,
                             const orbfe_feature_vector* fv2, int32_t* out12, float nnratio, int32_t checkOri) {
+    t_bow_form = ORBFE_BOW_FORM_NONE;
     if (n1 < 0 || n2 < 0 || !fv1 || !fv2 || (n1 > 0 && (!keys1 || !desc1 || !mp1 || !out12)) ||
         (n2 > 0 && (!keys2 || !desc2 || !mp2)) || nleft1 < -1 || nleft1 > n1 || nleft2 < -1 || nleft2 > n2)
         return ORBFE_E_ARG;
@@ -454,6 +455,7 @@ int orbfe_search_by_bow_kf2(const orbfe_keypoint* keys1, const uint8_t* desc1, c
     if (rc) return rc;
     MsTimer timer;
     hipStream_t s = t_ms.stream;
+    t_bow_form = ORBFE_BOW_FORM_KFKF;
     fill(ms_ptr<int>(o_m2), n2, 0);
     fill(ms_ptr<int>(o_oi), n1, -1);
     hipLaunchKernelGGL(k_bow_kfkf, dim3((npairs + MT_NT - 1) / MT_NT), dim3(MT_NT), 0, s, ms_ptr<const int>(o_pairs),

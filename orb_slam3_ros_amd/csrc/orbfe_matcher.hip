@@ -3674,6 +3674,9 @@ thread_local bool t_stats = false;
 thread_local long long t_last_stats[3] = {-1, -1, -1};
 // orbfe_matcher_last_form: the form sbp_run chose for the thread's last SearchByProjection (host record)
 thread_local int t_last_form = ORBFE_SBP_FORM_NONE;
+// orbfe_matcher_last_bow_form / _last_bow_batch: the same for the thread's last SearchByBoW call
+thread_local int t_bow_form = ORBFE_BOW_FORM_NONE;
+thread_local int t_bow_batch[3] = {0, 0, 0};   // one workgroup, empty row, multi-launch
 thread_local float t_last_ms = -1.f;
 thread_local hipEvent_t t_ev[2] = {nullptr, nullptr};
 struct MsTimer {
@@ -4954,6 +4957,7 @@ static int sfi_core(const orbfe_frame* F1, const orbfe_frame* F2, float* prev_ma
 int orbfe_search_by_bow(const orbfe_keypoint* kf_keys, const uint8_t* kf_desc, const int32_t* kf_mp, int32_t kf_n,
                         const orbfe_feature_vector* kf_fv, const orbfe_frame* F, const orbfe_feature_vector* f_fv,
                         int32_t* out, float nnratio, int32_t checkOri) {
+    t_bow_form = ORBFE_BOW_FORM_NONE;   // a refused or empty search ran none
     if (!F || F->n < 0 || kf_n < 0 || !kf_fv || !f_fv || !out || (kf_n > 0 && (!kf_keys || !kf_desc || !kf_mp)))
         return ORBFE_E_ARG;
     if (F->two_cams && (F->nleft < 0 || F->nleft > F->n)) return ORBFE_E_ARG;
@@ -5018,6 +5022,7 @@ int orbfe_search_by_bow(const orbfe_keypoint* kf_keys, const uint8_t* kf_desc, c
         MatchScratch& m = t_ms;
         auto rel = [&](size_t o) { return (int)(o - o_pairs); };
         const int seq = ++t_ms.seq;
+        t_bow_form = ORBFE_BOW_FORM_BLOCK;
         BowBlockIn in{up_ptr<const uint4>(o_pairs, true), (int)((reg_bytes + 15) / 16), rel(o_pairs), rel(o_kfoff),
                       rel(o_kfidx), rel(o_foff), rel(o_fidx), rel(o_kfmp), rel(o_kfdesc), rel(o_kfkeys), rel(o_fdesc),
                       up_ptr<const OrbKeyPoint>(o_fkeys, true), npairs, kf_n, fn, F->two_cams ? F->nleft : -1,
@@ -5030,6 +5035,7 @@ int orbfe_search_by_bow(const orbfe_keypoint* kf_keys, const uint8_t* kf_desc, c
         memcpy(out, m.ho, (size_t)fn * 4);   // complete: the status words come after the output stores
         return st[1];
     }
+    t_bow_form = ORBFE_BOW_FORM_NODES;
     fill(ms_ptr<int>(o_src), fn, -1);
     hipLaunchKernelGGL(k_bow_nodes, dim3((npairs + MT_NT - 1) / MT_NT), dim3(MT_NT), 0, s, ms_ptr<const int>(o_pairs),
                        npairs, ms_ptr<const int>(o_kfoff), ms_ptr<const uint32_t>(o_kfidx), ms_ptr<const int>(o_foff),
@@ -5125,6 +5131,7 @@ int orbfe_keyframe_n(const orbfe_keyframe* kf) { return kf ? kf->n : ORBFE_E_ARG
 int orbfe_search_by_bow_batch(const orbfe_keyframe* const* kfs, const int32_t* const* kf_mp, int32_t n_kfs,
                               const orbfe_frame* F, const orbfe_feature_vector* f_fv, int32_t* out, int32_t* nmatches,
                               float nnratio, int32_t checkOri) {
+    t_bow_batch[0] = t_bow_batch[1] = t_bow_batch[2] = 0;
     if (n_kfs < 0 || !out || !nmatches) return ORBFE_E_ARG;
     if (n_kfs == 0) return ORBFE_OK;
     if (!kfs || !kf_mp || !F || F->n < 0 || !f_fv || f_fv->n_nodes < 0) return ORBFE_E_ARG;
@@ -5138,6 +5145,7 @@ int orbfe_search_by_bow_batch(const orbfe_keyframe* const* kfs, const int32_t* c
         any = any || (kfs[c] && kfs[c]->bow);
     }
     for (size_t i = 0; i < (size_t)n_kfs * fn; i++) out[i] = -1;
+    t_bow_batch[1] = n_kfs;   // the rows above are the result of a call that ends before the launch
     if (fn == 0 || fnn == 0 || !any) return ORBFE_OK;
     if (!f_fv->node_ids || !f_fv->offsets || f_fv->offsets[0] != 0) return ORBFE_E_ARG;
     for (int i = 0; i < fnn; i++)
@@ -5202,6 +5210,8 @@ int orbfe_search_by_bow_batch(const orbfe_keyframe* const* kfs, const int32_t* c
         if (cd.mode == 2) o_pairs[c] = p.upload(pairs[c].data(), pairs[c].size() * 4);
     }
     for (int c = 0; c < n_kfs; c++) cands[c].mp_vec = (int)((o_mp[c] - o_fnid) / 16);
+    t_bow_batch[1] = 0;
+    for (int c = 0; c < n_kfs; c++) t_bow_batch[cands[c].mode]++;
     const size_t o_cands = p.upload(cands.data(), (size_t)n_kfs * sizeof(BowCand));
     for (int c = 0; c < n_kfs; c++)
         if (cands[c].mode == 2) o_src[c] = p.scratch((size_t)fn * 4);
@@ -5475,6 +5485,12 @@ int orbfe_matcher_last_stats(long long* out) {
 }
 
 int orbfe_matcher_last_form(void) { return t_last_form; }
+int orbfe_matcher_last_bow_form(void) { return t_bow_form; }
+int orbfe_matcher_last_bow_batch(int32_t* out) {
+    if (!out) return ORBFE_E_ARG;
+    for (int i = 0; i < 3; i++) out[i] = t_bow_batch[i];
+    return ORBFE_OK;
+}
 
 float orbfe_matcher_last_ms(void) { return t_last_ms; }
 
