@@ -420,6 +420,29 @@ int orbfe_search_by_bow_batch(const orbfe_keyframe* const* kfs, const int32_t* c
                               const orbfe_frame* F, const orbfe_feature_vector* f_fv, int32_t* out,
                               int32_t* nmatches, float nnratio, int32_t checkOri);
 
+/* SearchByBoW(pKF1, pKF2[c], vpMatches12[c]) (ORBmatcher.cc:765-903) for c in [0, n_kfs) in one call and
+ * one kernel launch, one workgroup per candidate: the SearchByBoW(mpCurrentKF, vpCovKFi[j], ...) calls of
+ * LoopClosing::DetectCommonRegionsFromBoW (LoopClosing.cc:1596-1705). kf1: the query keyframe, resident
+ * (orbfe_keyframe_create); mp1: [orbfe_keyframe_n(kf1)] GetMapPointMatches() handles with NULL / bad
+ * points as -1, host memory, read once per call. kfs2[c]: a resident candidate; NULL is a bad or
+ * discarded one: its row is all -1 and nmatches[c] = 0. mp2[c]: [orbfe_keyframe_n(kfs2[c])] handles,
+ * host memory, the only per-candidate upload (ignored for NULL). nleft1 / nleft2[c]: NLeft of a
+ * two-camera keyframe as in orbfe_search_by_bow_kf2, -1 for a single camera; nleft2 == NULL means all
+ * -1. out12: [n_kfs][orbfe_keyframe_n(kf1)] KF2 handles or -1; nmatches: [n_kfs]. Row c and
+ * nmatches[c] are bit-identical to out12 and the return value of orbfe_search_by_bow_kf2 on the arrays
+ * the handles were created from. A candidate that does not fit one workgroup's LDS takes the
+ * multi-launch kernels inside the same call, without re-uploading either keyframe. The results are
+ * complete on return, after one host wait.
+ * n_kfs == 0 returns ORBFE_OK. ORBFE_E_ARG, before any device work and before any write: n_kfs < 0, a
+ * NULL out12 / nmatches / kf1 / kfs2 / mp2, a NULL mp1 or mp2[c] of a keyframe with features, nleft1
+ * outside [-1, n1] or nleft2[c] outside [-1, n2[c]], a handle of another device, a handle whose
+ * FeatureVector names an index in two nodes (orbfe_search_by_bow_kf2 refuses those arrays too).
+ * Returns ORBFE_OK or a negative code. */
+int orbfe_search_by_bow_kf_batch(const orbfe_keyframe* kf1, const int32_t* mp1, int32_t nleft1,
+                                 const orbfe_keyframe* const* kfs2, const int32_t* const* mp2,
+                                 const int32_t* nleft2, int32_t n_kfs, int32_t* out12, int32_t* nmatches,
+                                 float nnratio, int32_t checkOri);
+
 /* ComputeStereoFishEyeMatches' descriptor stage (Frame.cc:1126-1151): BFMatcher(NORM_HAMMING)
  * knnMatch(k=2) of left rows [0, nl) against right rows [0, nr) and Lowe's 0.7 ratio. out_train[i]
  * = best right row of left row i or -1; out_dist[i] its distance. The KannalaBrandt8
@@ -899,6 +922,39 @@ int orbfe_kfdb_detect_reloc(orbfe_kfdb* db, const uint32_t* f_word_ids, const do
                             int32_t map_id, orbfe_kf_info_fn info, void* ctx, int32_t* out_ids, int32_t cap,
                             int32_t* n_out);
 
+/* KeyFrameDatabase::DetectNBestCandidates(pKF, vpLoopCand, vpMergeCand, nNumCandidates) (:604-730):
+ * the loop candidates (keyframes of map_id) and merge candidates (keyframes of another map that is not
+ * in bad_map_ids) as keyframe ids in the reference's order, at most n_candidates each (the capacity of
+ * loop_ids and merge_ids). q_*: pKF->mBowVec; connected_ids: pKF->GetConnectedKeyFrames() (ids absent
+ * from the database are ignored); map_id: pKF->GetMap(); info as for orbfe_kfdb_detect_reloc (NULL: no
+ * neighbours, every keyframe in map_id).
+ * Stages 1 and 2 are the device query of orbfe_kfdb_detect_reloc. Connected keyframes leave
+ * lKFsSharingWords before maxCommonWords is taken (:626), so they move the gate
+ * int(maxCommonWords * 0.8f); the rest keeps the list order; the score is the same L1 double chain
+ * rounded to float. mPlaceRecognitionScore is a field of the database entry apart from mRelocScore:
+ * neither query reads or writes the other's, erase drops both. The covisibility pass (:675-700) runs on
+ * the host in float: a neighbour counts if it is in the database, shares a word with the query and is
+ * not connected; its stored mPlaceRecognitionScore is added whether this query scored it or not (a
+ * stale score counts, as in the reference); accScore accumulates in neighbour order and pBestKF is the
+ * strictly greater score. The list is then sorted by accScore, descending and stable (std::list::sort),
+ * and walked while either output is short of n_candidates: a keyframe seen before is skipped, one of
+ * map_id goes to loop_ids if there is room, one of another map to merge_ids if there is room and the
+ * map is not bad (:707-729).
+ * Departures from the reference: every call is a fresh query (the reference stamps with pKF->mnId, so a
+ * second query by the same keyframe would see the first one's stamps; LoopClosing never asks twice), so
+ * the "shares a word and is not connected" stamp lives for the call only; and the isBad() branch of the
+ * walk (:712, which would never advance) has no counterpart, a bad keyframe having been erased.
+ * ORBFE_E_ARG before any device call: a NULL handle, n_loop or n_merge, NULL loop_ids / merge_ids with
+ * n_candidates > 0, n_candidates < 0, a negative count, a NULL array with a positive count, word ids
+ * that do not strictly ascend or reach n_words. An info that answers outside 0..10: ORBFE_E_ARG. A
+ * refused call writes no output and changes no state. An empty query or an empty database: ORBFE_OK
+ * with both counts 0. */
+int orbfe_kfdb_detect_nbest(orbfe_kfdb* db, const uint32_t* q_word_ids, const double* q_weights, int32_t q_n,
+                            const int32_t* connected_ids, int32_t n_connected, int32_t map_id,
+                            const int32_t* bad_map_ids, int32_t n_bad_maps, int32_t n_candidates,
+                            orbfe_kf_info_fn info, void* ctx, int32_t* loop_ids, int32_t* n_loop,
+                            int32_t* merge_ids, int32_t* n_merge);
+
 /* ---------------------------------------------------------------------------------------------
  * Stereo rectification: cv::remap(im, out, M1, M2, cv::INTER_LINEAR) with CV_32F
  * maps from initUndistortRectifyMap (System.cc:233-240, Settings.cc:506-509), BORDER_CONSTANT 0.
@@ -967,6 +1023,11 @@ enum {
 };
 int orbfe_matcher_last_bow_form(void);
 int orbfe_matcher_last_bow_batch(int32_t* out);
+/* The same three counts for this thread's last orbfe_search_by_bow_kf_batch: out[0] matched in
+ * k_bow_kfkf_batch's one workgroup, out[1] got the empty row (NULL, no features or FeatureVector on
+ * either side, no node shared with KF1, or a call that returned before any launch), out[2] took
+ * k_bow_kfkf + k_bow_kfkf_commit_ang. */
+int orbfe_matcher_last_bow_kf_batch(int32_t* out);
 
 /* Debug/inspection (tests only): copy an intermediate of image `image`, level `level` of the last
  * batch to host memory. what: 0 = per-cell FAST key counts (int32[n_cells]),

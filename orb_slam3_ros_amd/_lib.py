@@ -162,6 +162,10 @@ _SIGS = {
     "orbfe_kfdb_add_batch": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _vp]),
     "orbfe_search_by_projection_kf_batch": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _vp, _vp, _c_float,
                                                      _c_int, _c_int]),
+    "orbfe_search_by_bow_kf_batch": (_c_int, [_vp, _vp, _c_int, _vp, _vp, _vp, _c_int, _vp, _vp, _c_float, _c_int]),
+    "orbfe_matcher_last_bow_kf_batch": (_c_int, [_vp]),
+    "orbfe_kfdb_detect_nbest": (_c_int, [_vp, _vp, _vp, _c_int, _vp, _c_int, _c_int, _vp, _c_int, _c_int, KF_INFO_FN,
+                                         _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

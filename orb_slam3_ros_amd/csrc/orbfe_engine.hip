@@ -1528,3 +1528,7 @@ int orbfe_descriptor_distance(const uint8_t* a, const uint8_t* b) {
 
 // Batched ComputeBoW on device-resident frames, and its path into the keyframe database.
 #include "orbfe_bow_batch.hip"
+
+// Loop-closure place recognition: batched SearchByBoW(KF1, KF2) over resident keyframes and
+// DetectNBestCandidates on the keyframe database.
+#include "orbfe_place.hip"

@@ -107,6 +107,7 @@ struct orbfe_kfdb {
         int32_t id;
         float reloc_score;   // KeyFrame::mRelocScore
         bool live;
+        float place_score = 0.f;   // KeyFrame::mPlaceRecognitionScore (orbfe_kfdb_detect_nbest; apart from reloc_score)
     };
     std::vector<Entry> ent;
     std::vector<int2> h_ent;

@@ -4668,6 +4668,7 @@ struct orbfe_keyframe {
     int n = 0, nn = 0;
     uint8_t* pack = nullptr;   // n > 0
     bool bow = false;          // the pack holds a FeatureVector with indices (else SearchByBoW's row is empty)
+    bool unique = true;        // every index sits in one node only (orbfe_search_by_bow_kf_batch requires it of both sides)
     int nvec = 0;
     int o_off = 0, o_idx = 0, o_ang = 0, o_desc = 0;
     std::vector<uint32_t> node_ids;
@@ -5080,6 +5081,13 @@ int orbfe_keyframe_create(const orbfe_frame* KF, const orbfe_feature_vector* fv,
     if (n == 0) {   // nothing to match: no pack, every search gives the empty row
         *out = kf.release();
         return ORBFE_OK;
+    }
+    {
+        std::vector<uint8_t> seen(n, 0);
+        for (int i = 0; i < nki; i++) {
+            if (seen[fv->indices[i]]) kf->unique = false;
+            seen[fv->indices[i]] = 1;
+        }
     }
     kf->bow = nki > 0;   // an empty FeatureVector: SearchByBoW's row is empty, the angles still serve SearchByProjection
     kf->nvec = (int)(total / 16);

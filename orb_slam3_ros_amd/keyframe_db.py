@@ -132,6 +132,46 @@ class KeyFrameDatabase:
         _lib.check(rc, "DetectRelocalizationCandidates")
         return out[:n.value].copy()
 
+    def DetectNBestCandidates(self, bow, connected, map_id: int = 0, n: int = 3, neighbours=None, maps=None,
+                              bad_maps=()):
+        """DetectNBestCandidates(pKF, vpLoopCand, vpMergeCand, n) (KeyFrameDatabase.cc:604-730) ->
+        (loop_ids, merge_ids), int32 arrays of at most n keyframe ids each. bow: pKF->mBowVec; connected:
+        pKF->GetConnectedKeyFrames() as ids; map_id: pKF->GetMap(); neighbours / maps as for
+        DetectRelocalizationCandidates; bad_maps: ids of the maps with IsBad()."""
+        ids, w = _bow(bow)
+        con = np.ascontiguousarray(list(connected), np.int32).reshape(-1)
+        bad = np.ascontiguousarray(list(bad_maps), np.int32).reshape(-1)
+        n = int(n)
+        # the callback-error protocol of DetectRelocalizationCandidates
+        err = []
+
+        def info(ctx, kf_id, nb, mp):
+            mp[0] = int(map_id)
+            if err:
+                return -1
+            try:
+                mp[0] = int(_lookup(maps, kf_id, map_id))
+                ns = list(_lookup(neighbours, kf_id, ()))[:10]
+                for i, v in enumerate(ns):
+                    nb[i] = int(v)
+                return len(ns)
+            except BaseException as ex:  # noqa: BLE001 - re-raised below
+                err.append(ex)
+                return -1
+
+        cb = _lib.KF_INFO_FN(info) if (neighbours is not None or maps is not None) else _lib.KF_INFO_FN()
+        loop = np.zeros(max(n, 1), np.int32)
+        merge = np.zeros(max(n, 1), np.int32)
+        nl, nm = ctypes.c_int32(0), ctypes.c_int32(0)
+        rc = self._lib.orbfe_kfdb_detect_nbest(self._h, ids.ctypes.data, w.ctypes.data, len(ids),
+                                               con.ctypes.data if len(con) else None, len(con), int(map_id),
+                                               bad.ctypes.data if len(bad) else None, len(bad), n, cb, None,
+                                               loop.ctypes.data, ctypes.byref(nl), merge.ctypes.data, ctypes.byref(nm))
+        if err:
+            raise err[0]
+        _lib.check(rc, "DetectNBestCandidates")
+        return loop[:nl.value].copy(), merge[:nm.value].copy()
+
     def close(self) -> None:
         if self._h:
             self._lib.orbfe_kfdb_destroy(self._h)

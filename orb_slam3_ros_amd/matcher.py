@@ -513,6 +513,42 @@ class ORBmatcher:
             int(self.mbCheckOrientation)), "SearchByBoW(KF, KF)")
         return n, out
 
+    # the SearchByBoW(mpCurrentKF, vpCovKFi[j], vvpMatchedMPs[j]) calls of LoopClosing::DetectCommonRegionsFromBoW
+    # (LoopClosing.cc:1596-1705) in one call over resident keyframes
+    def SearchByBoWKFBatch(self, kf1, mp1, kfs2, mp2s, nleft1: int = -1, nleft2s=None):
+        """kf1: KeyFrameFeatures of the query keyframe; mp1: int32 [kf1.N] GetMapPointMatches() handles with
+        NULL / bad points as -1; kfs2: KeyFrameFeatures or None (a bad candidate) per candidate; mp2s[c]:
+        int32 [kfs2[c].N] (ignored for None); nleft1 / nleft2s[c]: NLeft of a two-camera keyframe, -1
+        otherwise (nleft2s None: all -1). Returns (nmatches int32 [C], vpMatches12 int32 [C, kf1.N]); row c
+        equals SearchByBoWKF on candidate c."""
+        C = len(kfs2)
+        if len(mp2s) != C or (nleft2s is not None and len(nleft2s) != C):
+            raise ValueError("one mp2s / nleft2s entry per candidate")
+        if kf1 is None or kf1.handle is None:
+            raise ValueError("KeyFrameFeatures is closed")
+        m1 = _i32(np.ascontiguousarray(mp1, np.int32), kf1.N, "mp1")
+        handles = (ctypes.c_void_p * max(C, 1))()
+        mps = (ctypes.c_void_p * max(C, 1))()
+        keep = []
+        for c, kf in enumerate(kfs2):
+            if kf is None:
+                continue
+            if kf.handle is None:
+                raise ValueError("KeyFrameFeatures is closed")
+            km = _i32(np.ascontiguousarray(mp2s[c], np.int32), kf.N, "mp2s")
+            keep.append(km)
+            handles[c] = kf.handle
+            mps[c] = km.ctypes.data if kf.N else None
+        nl2 = None if nleft2s is None else np.ascontiguousarray(nleft2s, np.int32).reshape(-1)
+        out = np.full((C, kf1.N), -1, np.int32)
+        nm = np.zeros(C, np.int32)
+        if C:
+            _lib.check(self._lib.orbfe_search_by_bow_kf_batch(
+                kf1.handle, m1.ctypes.data if kf1.N else None, int(nleft1), handles, mps,
+                nl2.ctypes.data if nl2 is not None else None, C, out.ctypes.data, nm.ctypes.data, self.mfNNratio,
+                int(self.mbCheckOrientation)), "SearchByBoW(KF, KF batch)")
+        return nm, out
+
 
     # SearchForTriangulation(pKF1, pKF2, vMatchedPairs, bOnlyStereo, bCoarse) (:907-1146)
     def SearchForTriangulation(self, KF1: MatchFrame, mp1, fv1: FeatureVector, KF2: MatchFrame, mp2,
