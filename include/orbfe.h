@@ -727,6 +727,47 @@ int orbfe_search_by_projection_lastframe_pose(const orbfe_frame* cur, int32_t* m
                                               const orbfe_pose* Trl, const orbfe_camera_model* cam, float th,
                                               int32_t bForward, int32_t bBackward, int32_t checkOri);
 
+/* The same search for the frames of a batch extraction, in one call and one kernel launch, one workgroup
+ * per frame, on the slabs orbfe_extract_batch and orbfe_stereo_match_batch wrote (the layout of
+ * orbfe_batch_outputs / orbfe_set_batch_outputs), without a host copy of any frame. The frames of a batch
+ * are independent: each has its own pose, its own last-frame points and its own mvpMapPoints, which
+ * Tracking::TrackWithMotionModel fills with NULL before the search.
+ * One frame of the batch: */
+typedef struct orbfe_track_job {
+    orbfe_pose Tcw;                  /* CurrentFrame.GetPose() (kind ORBFE_SE3) */
+    const orbfe_last_point* pts;     /* host, LastFrame.mvpMapPoints order; NULL when n_pts == 0 */
+    int32_t n_pts;                   /* 0: frame skipped (row all -1, nmatches 0) */
+    float th;
+    int32_t bForward, bBackward;     /* as the reference computes them (ORBmatcher.cc:1691-1693) */
+} orbfe_track_job;                   /* 56 bytes */
+
+/* d_kps [image][cap], d_desc [image][cap][32], d_counts [image][2] = {n, monoIndex}: device slabs; frame f
+ * is image base + f*step. d_uright: device [nframes][cap] mvuRight rows (orbfe_stereo_match_batch's
+ * output) or NULL for monocular frames. geom (host): min_x .. max_y, mbf, nlevels and scale_factors are
+ * read, two_cams must be 0, nothing else is looked at. cam: CurrentFrame.mpCamera (pinhole or
+ * KannalaBrandt8), one camera for the whole batch. stream: the stream the slabs were written on; the launch
+ * runs on the calling thread's matcher stream after an event recorded on `stream`, so the caller does not
+ * synchronise after the extraction.
+ * Frame f's N = d_counts[2*(base + f*step)] is read on the device. Row f of mvp_out (host [nframes][cap])
+ * and nmatches[f] are bit-identical to orbfe_search_by_projection_lastframe_pose on that frame's N
+ * keypoints with mvp all -1 and mvp_obs all 0, job f's points, pose, th, bForward and bBackward; slots
+ * [N, cap) are -1; n_keys[f] = N. Rows never affect each other. A job with n_pts == 0 is skipped: its row
+ * is all -1 and nmatches[f] = 0 (the retry with 2*th is a second call with n_pts = 0 for the frames that
+ * passed). A frame with N == 0 gives nmatches[f] = 0. A frame whose N exceeds min(cap, 2048) cannot be
+ * refused on the host: its row is all -1 and nmatches[f] = ORBFE_E_CAPACITY, every other frame is
+ * unaffected. The results are complete on return. nframes == 0 returns ORBFE_OK.
+ * ORBFE_E_ARG: nframes < 0, a NULL d_kps / d_desc / d_counts / geom / cam / jobs / mvp_out / nmatches /
+ * n_keys, cap <= 0, a negative base or step, an n_pts < 0, NULL pts with n_pts > 0, a valid point whose
+ * octave is outside [0, nlevels), a bad model type, geom->two_cams, geom without levels or scale factors,
+ * a pose that is not ORBFE_SE3. ORBFE_E_CAPACITY: an n_pts > 2048, or bounds that do not fit the
+ * one-workgroup index. Every refusal comes before any device work and before any write to the outputs. */
+int orbfe_search_by_projection_lastframe_slabs(const orbfe_keypoint* d_kps, const uint8_t* d_desc,
+                                               const int32_t* d_counts, int32_t cap, int32_t base, int32_t step,
+                                               const float* d_uright, const orbfe_frame* geom,
+                                               const orbfe_camera_model* cam, const orbfe_track_job* jobs,
+                                               int32_t nframes, int32_t checkOri, int32_t* mvp_out, int32_t* nmatches,
+                                               int32_t* n_keys, void* stream);
+
 /* The matching half of Fuse (ORBmatcher.cc:1148-1337 with sim3 = 0; :1339-1455, Fuse(pKF, Scw, ...)
  * with sim3 = 1; pinhole, bRight = false): for every point with id >= 0 not flagged BAD / SKIP (SKIP =
  * IsInKeyFrame(pKF), resp. already in pKF->GetMapPoints()), project, check and search the keyframe
@@ -1028,6 +1069,10 @@ int orbfe_matcher_last_bow_batch(int32_t* out);
  * either side, no node shared with KF1, or a call that returned before any launch), out[2] took
  * k_bow_kfkf + k_bow_kfkf_commit_ang. */
 int orbfe_matcher_last_bow_kf_batch(int32_t* out);
+/* Of this thread's last orbfe_search_by_projection_lastframe_slabs: out[0] frames searched in
+ * k_sbp_track_batch's one workgroup, out[1] skipped (n_pts == 0 or no keypoints), out[2] over the
+ * workgroup's capacity (nmatches[f] = ORBFE_E_CAPACITY). All zero after a refused or empty call. */
+int orbfe_matcher_last_track_batch(int32_t* out);
 
 /* Debug/inspection (tests only): copy an intermediate of image `image`, level `level` of the last
  * batch to host memory. what: 0 = per-cell FAST key counts (int32[n_cells]),

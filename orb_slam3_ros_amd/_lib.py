@@ -166,6 +166,9 @@ _SIGS = {
     "orbfe_matcher_last_bow_kf_batch": (_c_int, [_vp]),
     "orbfe_kfdb_detect_nbest": (_c_int, [_vp, _vp, _vp, _c_int, _vp, _c_int, _c_int, _vp, _c_int, _c_int, KF_INFO_FN,
                                          _vp, _vp, _vp, _vp, _vp]),
+    "orbfe_search_by_projection_lastframe_slabs": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp,
+                                                            _c_int, _c_int, _vp, _vp, _vp, _vp]),
+    "orbfe_matcher_last_track_batch": (_c_int, [_vp]),
 }
 
 _lib = None

@@ -1532,3 +1532,6 @@ int orbfe_descriptor_distance(const uint8_t* a, const uint8_t* b) {
 // Loop-closure place recognition: batched SearchByBoW(KF1, KF2) over resident keyframes and
 // DetectNBestCandidates on the keyframe database.
 #include "orbfe_place.hip"
+
+// Batched motion-model SearchByProjection(CurrentFrame, LastFrame) over the frames of a batch extraction.
+#include "orbfe_track_batch.hip"

@@ -203,6 +203,23 @@ class StereoFrontEnd:
         was given). No host wait. -> vocabulary.BowBatch, allocated once and filled again by later calls."""
         return _compute_bow(self, voc, levelsup, stream)
 
+    def track_motion_model(self, jobs, geom, cam, stream=None, check_ori: bool = True):
+        """TrackWithMotionModel's SearchByProjection(CurrentFrame, LastFrame, th, bMono) for all F frames
+        of the last run() in one launch, on the left-image slabs (image 2f) and the uright rows of the
+        stereo match where run() left them: nothing is copied to the host first. jobs: F matcher.TrackJob
+        (pose, last-frame points, th, bForward / bBackward; no points = frame skipped); geom: a MatchFrame
+        with the frames' bounds, mbf and scale factors; cam: matcher.CameraModel. stream: the hipStream_t
+        run() was given (None: the caller's current torch stream, which run() ordered after its own).
+        -> (nmatches [F], n_keys [F], mvp [F, cap]) numpy int32, see ORBmatcher.SearchByProjectionLastFrameBatch."""
+        from .matcher import ORBmatcher
+        if self.stereo == "fisheye":
+            raise _lib.OrbfeError("track_motion_model searches single-camera frames (stereo 'rectified' or 'none')")
+        if len(jobs) != self.F:
+            raise ValueError(f"one job per frame: {self.F}")
+        return ORBmatcher(0.9, check_ori).SearchByProjectionLastFrameBatch(
+            self.kps, self.desc, self.counts, self.cap, 0, 2, self.uright if self.stereo == "rectified" else None,
+            geom, cam, jobs, stream=stream)
+
     def host_frame(self, f: int):
         """(kps_left structured, desc_left, uright, depth) of frame f, copied to the host."""
         _, kp, d = self.host_image(2 * f)

@@ -209,6 +209,26 @@ class KFCamera(ctypes.Structure):
         return c
 
 
+class TrackJob(ctypes.Structure):
+    """struct orbfe_track_job: one frame of ORBmatcher.SearchByProjectionLastFrameBatch (56 bytes)."""
+    _fields_ = [("Tcw", Pose), ("pts", ctypes.c_void_p), ("n_pts", ctypes.c_int32), ("th", ctypes.c_float),
+                ("bForward", ctypes.c_int32), ("bBackward", ctypes.c_int32)]
+
+    @staticmethod
+    def make(Tcw: Pose, points, th: float, bForward: bool = False, bBackward: bool = False):
+        """points: LAST_POINT records in LastFrame.mvpMapPoints order, or None / empty: the frame is
+        skipped. The job keeps the array alive."""
+        j = TrackJob()
+        j.Tcw = Tcw
+        pts = None if points is None else _records(points, LAST_POINT_DTYPE, "points")
+        j._points = pts
+        j.n_pts = 0 if pts is None else len(pts)
+        j.pts = pts.ctypes.data if j.n_pts else None
+        j.th = float(th)
+        j.bForward, j.bBackward = int(bool(bForward)), int(bool(bBackward))
+        return j
+
+
 class MatchFrame:
     """The parts of a Frame the matchers read (Frame.h). keys: KEYPOINT_DTYPE [n] (mvKeysUn),
     desc: uint8 [n, 32], bounds: (mnMinX, mnMaxX, mnMinY, mnMaxY), uright: float32 [n] or None.
@@ -370,6 +390,52 @@ class ORBmatcher:
             cur.ref(), mvp.ctypes.data, mvp_obs.ctypes.data, pts.ctypes.data, len(pts), ctypes.byref(Tcw),
             ctypes.byref(Trl) if Trl is not None else None, ctypes.byref(cam), float(th), int(bForward),
             int(bBackward), int(self.mbCheckOrientation)), "SearchByProjection(last frame, device projection)")
+
+    # TrackWithMotionModel's search for every frame of a batch extraction in one call, on the device slabs
+    def SearchByProjectionLastFrameBatch(self, kps, desc, counts, cap: int, base: int, step: int, uright, geom, cam,
+                                         jobs, stream=None):
+        """kps [images, cap, 7] int32, desc [images, cap, 32] uint8, counts [images, 2] int32: contiguous
+        CUDA tensors in the layout of the extractor's batch outputs; frame f is image base + f * step.
+        uright: float32 CUDA tensor [len(jobs), cap] (mvuRight rows) or None for monocular frames. geom: a
+        MatchFrame-like object whose bounds, mbf and scale factors describe every frame (its keypoints are
+        not read). cam: CameraModel. jobs: TrackJob per frame. stream: the hipStream_t the slabs were
+        written on (None: the current torch stream of the slabs' device).
+        Returns (nmatches int32 [B], n_keys int32 [B], mvp int32 [B, cap]); row f equals
+        SearchByProjectionLastFramePose on frame f's keypoints with empty slots, -1 beyond its count.
+        nmatches[f] is _lib.ORBFE_E_CAPACITY for a frame of more than 2048 keypoints."""
+        import torch
+        B, cap = len(jobs), int(cap)
+        for t, dt, tail, what in ((kps, torch.int32, (cap, 7), "kps"), (desc, torch.uint8, (cap, 32), "desc"),
+                                  (counts, torch.int32, (2,), "counts")):
+            if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.dim() == len(tail) + 1
+                    and tuple(t.shape[1:]) == tail):
+                raise ValueError(f"{what} must be a contiguous CUDA {dt} tensor of shape [images, {tail}]")
+        nimg = int(counts.shape[0])
+        if kps.shape[0] != nimg or desc.shape[0] != nimg:
+            raise ValueError("kps, desc and counts hold different numbers of images")
+        if base < 0 or step < 0 or (B > 0 and base + (B - 1) * step >= nimg):
+            raise ValueError("base + f * step leaves the slabs")
+        if uright is not None and not (uright.is_cuda and uright.dtype == torch.float32 and uright.is_contiguous()
+                                       and uright.dim() == 2 and uright.shape[0] >= B and uright.shape[1] == cap):
+            raise ValueError("uright must be a contiguous CUDA float32 tensor [frames, cap]")
+        arr = (TrackJob * max(B, 1))()
+        for f, j in enumerate(jobs):
+            if not isinstance(j, TrackJob):
+                raise ValueError("jobs must hold TrackJob structures")
+            arr[f] = j
+        if stream is None:
+            stream = torch.cuda.current_stream(kps.device).cuda_stream
+        mvp = np.full((B, cap), -1, np.int32)
+        nm = np.zeros(B, np.int32)
+        nk = np.zeros(B, np.int32)
+        if B:
+            with torch.cuda.device(kps.device):
+                _lib.check(self._lib.orbfe_search_by_projection_lastframe_slabs(
+                    kps.data_ptr(), desc.data_ptr(), counts.data_ptr(), cap, int(base), int(step),
+                    uright.data_ptr() if uright is not None else None, geom.ref(), ctypes.byref(cam), arr, B,
+                    int(self.mbCheckOrientation), mvp.ctypes.data, nm.ctypes.data, nk.ctypes.data, stream),
+                    "SearchByProjection(last frame, batch)")
+        return nm, nk, mvp
 
     # SearchByProjection(Frame&, KeyFrame*, const set<MapPoint*>&, th, ORBdist) (:1889-2010)
     def SearchByProjectionKeyFrame(self, cur: MatchFrame, mvp, points, th: float, ORBdist: int) -> int:
