@@ -1073,6 +1073,11 @@ int orbfe_matcher_last_bow_kf_batch(int32_t* out);
  * k_sbp_track_batch's one workgroup, out[1] skipped (n_pts == 0 or no keypoints), out[2] over the
  * workgroup's capacity (nmatches[f] = ORBFE_E_CAPACITY). All zero after a refused or empty call. */
 int orbfe_matcher_last_track_batch(int32_t* out);
+/* The number of k_kf_search passes of this thread's last orbfe_search_by_projection_sim3(_rig): the
+ * reference's sequential "keypoint already matched" dependency needs one pass per link of a chain of
+ * queries that each lose their best keypoint to the query before. The driver runs the passes in pairs and
+ * reads the change flag after each pair, so the count is even. 0 after a refused or empty call. */
+int orbfe_matcher_last_sim3_passes(void);
 
 /* Debug/inspection (tests only): copy an intermediate of image `image`, level `level` of the last
  * batch to host memory. what: 0 = per-cell FAST key counts (int32[n_cells]),

@@ -527,6 +527,9 @@ bool octaves_ok(const orbfe_frame* F) {
     return true;
 }
 
+// orbfe_matcher_last_sim3_passes: k_kf_search passes of the thread's last SearchByProjection(Sim3)
+thread_local int t_sim3_passes = 0;
+
 bool pose_ok(const orbfe_pose* p) { return p && (p->kind == ORBFE_SE3 || p->kind == ORBFE_SIM3); }
 
 bool fv_ok(const orbfe_feature_vector* fv, int n) {
@@ -801,6 +804,7 @@ int orbfe_search_by_projection_sim3_rig(const orbfe_frame* KF, const orbfe_kf_ca
                                         const orbfe_camera_model* model, const orbfe_map_point_3d* pts, int32_t n,
                                         const int32_t* point_kfs, int32_t th, float ratioHamming, int32_t* matched,
                                         int32_t* matched_kf) {
+    t_sim3_passes = 0;
     if (!frame_ok(KF) || !cam || !pose_ok(&cam->Tcw) || n < 0 || (n > 0 && !pts) || (KF->n > 0 && !matched) ||
         (point_kfs && KF->n > 0 && !matched_kf) ||
         (model && model->type != ORBFE_CAM_PINHOLE && model->type != ORBFE_CAM_KANNALA_BRANDT8))
@@ -869,6 +873,7 @@ int orbfe_search_by_projection_sim3_rig(const orbfe_frame* KF, const orbfe_kf_ca
         MSCHK(ms_read_int(changed + pass - 1, s, ch));
         if (ch == 0) break;
     }
+    t_sim3_passes = pass;
     HIPCHK(hipMemsetAsync(ms_ptr<int>(o_cnt), 0, 4, s));
     hipLaunchKernelGGL(k_kf_commit, gq, dim3(MT_NT), 0, s, assign, n, ms_ptr<const orbfe_map_point_3d>(o_pts),
                        point_kfs ? ms_ptr<const int32_t>(o_pk) : nullptr, ms_ptr<int32_t>(o_m),
@@ -957,5 +962,7 @@ int orbfe_search_by_sim3(const orbfe_frame* KF1, const orbfe_frame* KF2, const o
     MSCHK(ms_read_int(ms_ptr<int>(o_cnt), s, nf));
     return nf;
 }
+
+int orbfe_matcher_last_sim3_passes(void) { return t_sim3_passes; }
 
 }  // extern "C"

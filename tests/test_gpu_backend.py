@@ -5,6 +5,8 @@ oracle (oracle/orb_oracle_match.cpp):
  * MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:329-403): chosen row per point for set
    sizes 0..2048 (LDS-staged and global-row paths), duplicate rows (first minimum wins).
 Parity is "unpinned" w.r.t. the real reference (no buildable reference, no fixtures): DESIGN.md.
+These are random scenes; the values at which each rule of Fuse, the Sim3 searches and triangulation
+decides are planted in tests/backend_patterns.py and run by tests/test_gpu_backend_adversarial.py.
 """
 import numpy as np
 import pytest
