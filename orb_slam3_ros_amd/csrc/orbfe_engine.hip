@@ -1137,8 +1137,11 @@ int orbfe_stereo_match_batch(orbfe_extractor* left, int lbase, int lstep, orbfe_
     // right side: redundant work, but the frame's chain of keypoints per wave is what bounds batch 1)
     const int lkpb = nframes < kSmallBatch ? kSmallStereoLk : ST_LK;
     StereoArgs sa{bf, fx, g.kp_cap, sort_cap, lkpb};
+    // right descriptors (later the block's results: 12 B per left keypoint, at most kp_cap of them) and
+    // records, sort keys, 16 KB of sort scratch (later the work list: 16 B per left keypoint of a block,
+    // lkpb <= ST_LK), the row-start table and the level table
     const size_t lds = (size_t)g.kp_cap * (32 + sizeof(RightRec)) + (size_t)sort_cap * 4 + (ST_NT / 64) * (512 + 128 * 4) +
-                       (size_t)round_up(2 * (g.height + 2 * ST_ROFF), 16);
+                       (size_t)round_up(2 * (g.height + 2 * ST_ROFF), 16) + ORBFE_MAX_LEVELS * sizeof(StLevel);
     if (lds > 160 * 1024 - 64 || g.kp_cap > 65535) return ORBFE_E_ARG;   // LDS: about 2700 keypoints per image
     hipStream_t s = pick_stream(left, stream);
     std::lock_guard<std::mutex> lk(left->mu_stereo);

@@ -2568,22 +2568,51 @@ __device__ __forceinline__ int hamming32(const uint32_t* a, const uint32_t* b) {
     for (int i = 0; i < 8; i++) d += __popc(a[i] ^ b[i]);
     return d;
 }
-// Stage 1: one wave per left keypoint at a time (16 waves per block, keypoints taken from a block
-// counter), ST_LK left keypoints per block; the right
-// keypoints (x, row band, octave) and descriptors of the frame are staged in LDS once per block
-// and the records are sorted by the first row of their band, so a left keypoint on row v scans
-// only the records with minr in [v - maxspan, v] (the reference's vRowIndices[v] superset; the
-// first-best-in-iR-order rule is kept by the (dist, iR) key).
-// Writes per left kp: uRight, depth (-1 = none) and the SAD distance of an accepted match (-1).
-#define ST_LK 512   // left keypoints per block (2 blocks per frame: 256 measured 10 % slower, 1024 20 %)
+// Stage 1, ST_LK left keypoints per block (16 waves), in two block-wide phases whose loops have a
+// static memory-op pattern (unconditional loads, no global stores). The right keypoints (x, row
+// band, octave) and descriptors of the frame are staged in LDS once per block and the records are
+// sorted by the first row of their band, so a left keypoint on row v scans only the records with
+// minr in [v - maxspan, v] (the reference's vRowIndices[v] superset; the first-best-in-iR-order
+// rule is kept by the (dist, iR) key).
+//   Phase A (match): 16 lanes per left keypoint, four keypoints per wave at a time, the next
+//     round's record and descriptor loaded ahead. The candidate scan, the (dist << 16) | iR minimum
+//     and the reference's tests that need no pixels; a keypoint that passes them appends a work item
+//     to an LDS list (wave-aggregated counter). No pyramid access.
+//   Phase B (SAD refinement over the list): 16 lanes per item, lane yy < 11 holding row yy of the
+//     11x11 left and 11x21 right windows in registers; the next round's rows are loaded before the
+//     current round's SADs. Every item passed the bounds test, so the loads are unconditional
+//     (idle lanes and rounds past the list repeat a valid item's addresses). The 11 row SADs of
+//     each shift are summed over the lanes by DPP; results go to LDS (the dead right descriptors).
+//   Epilogue: the block's uRight, depth (-1 = none) and SAD distance (-1) in coalesced stores.
+#define ST_LK 512   // left keypoints per block (2 blocks per frame)
 #define ST_NT 1024
 #define ST_ROFF 32    // row-start table margin (rows -32 .. height + 32)
 struct RightRec { float x; int minr, maxr, oct; };
+struct StLevel { int pitch, pyr_off, w; float scale, inv_scale; int pad[3]; };   // per-lane level lookups, in LDS
+// the work list (16 B per left keypoint of the block) takes the 16 KB of sort scratch after set-up
+static_assert(ST_LK * 16 <= (ST_NT / 64) * (512 + 128 * 4), "k_stereo: work list exceeds the sort scratch");
+// minimum over each 16-lane row, left in the row's lane 15. Every lane must be active.
+__device__ __forceinline__ int row16_min_dpp(int v) {
+    v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x111, 0xf, 0xf, false));
+    v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x112, 0xf, 0xf, false));
+    v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x114, 0xf, 0xf, false));
+    v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x118, 0xf, 0xf, false));
+    return v;
+}
+// sum over each 16-lane row, left in the row's lane 15. Every lane must be active.
+__device__ __forceinline__ uint32_t row16_sum_dpp(uint32_t u) {
+    int v = (int)u;
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);
+    return (uint32_t)v;
+}
 __global__ __launch_bounds__(ST_NT) void k_stereo(OrbGeom g, StereoSide SL, StereoSide SR, StereoArgs sa,
                                                   float* uright, float* depth, int* sdist) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem_st[];
     __shared__ int s_maxspan;
-    __shared__ int s_next;   // next left keypoint of the block (waves take them dynamically)
+    __shared__ int s_nitem;   // length of the work list
     const int lb = xcd_logical(block_linear(), gridDim.x * gridDim.y);
     const int f = lb / gridDim.x;
     const int bL = SL.base + f * SL.step, bR = SR.base + f * SR.step;
@@ -2601,13 +2630,12 @@ __global__ __launch_bounds__(ST_NT) void k_stereo(OrbGeom g, StereoSide SL, Ster
     uint32_t* s_descR = (uint32_t*)smem_st;                        // sa.max_kp * 8 words
     RightRec* s_rec = (RightRec*)(s_descR + 8 * sa.max_kp);        // sa.max_kp records
     uint32_t* s_key = (uint32_t*)(s_rec + sa.max_kp);              // sort keys, sa.sort_cap entries
-    uint8_t* s_win = (uint8_t*)(s_key + sa.sort_cap) + wave * 512; // per wave: IL 11x11 @0, IR 11x21 @128
-    int* s_part = (int*)((uint8_t*)(s_key + sa.sort_cap) + (ST_NT / 64) * 512) + wave * 128;
+    uint8_t* s_scr = (uint8_t*)(s_key + sa.sort_cap);              // 16 KB: sort scratch, then the work list
     const OrbKeyPoint* kR = SR.kps + (size_t)bR * g.kp_cap;
     const OrbKeyPoint* kL = SL.kps + (size_t)bL * g.kp_cap;
     const uint4* dR = (const uint4*)(SR.desc + (size_t)bR * g.kp_cap * 32);
     const uint32_t* dL = (const uint32_t*)(SL.desc + (size_t)bL * g.kp_cap * 32);
-    if (threadIdx.x == 0) { s_maxspan = 0; s_next = ST_NT / 64; }
+    if (threadIdx.x == 0) { s_maxspan = 0; s_nitem = 0; }
     SYNC();
     for (int i = threadIdx.x; i < Nr * 2; i += blockDim.x) ((uint4*)s_descR)[i] = dR[i];
     int span = 0;
@@ -2631,13 +2659,21 @@ __global__ __launch_bounds__(ST_NT) void k_stereo(OrbGeom g, StereoSide SL, Ster
     SYNC();
     // row -> first sorted record with minr >= row (rows -ST_ROFF .. height + ST_ROFF): the candidate
     // scan of a left keypoint reads one table entry per bound instead of a binary search
-    uint16_t* s_rowst = (uint16_t*)((uint8_t*)(s_key + sa.sort_cap) + (ST_NT / 64) * (512 + 128 * 4));
+    uint16_t* s_rowst = (uint16_t*)(s_scr + (ST_NT / 64) * (512 + 128 * 4));
+    StLevel* s_lv = (StLevel*)((uint8_t*)s_rowst + ((2 * nrow + 15) & ~15));
+    if (threadIdx.x < ORBFE_MAX_LEVELS) {
+        const OrbLevel& L = g.lv[threadIdx.x];
+        StLevel t;
+        t.pitch = L.pitch; t.pyr_off = L.pyr_off; t.w = L.w; t.scale = L.scale; t.inv_scale = L.inv_scale;
+        t.pad[0] = t.pad[1] = t.pad[2] = 0;
+        s_lv[threadIdx.x] = t;
+    }
     if (csort) {
         // counting sort by the first row of the band (clamped into the table; a clamped record only
         // moves towards the rows that can hold it, and the band test filters it): the order within
         // a row is immaterial, the scan keeps the first best in iR order through its (dist, iR) key.
-        // Counts and cursors in the waves' SAD scratch, free until the keypoint loop.
-        int* s_cnt = (int*)((uint8_t*)(s_key + sa.sort_cap) + (ST_NT / 64) * 512);
+        // Counts and cursors in the second half of the sort scratch.
+        int* s_cnt = (int*)(s_scr + (ST_NT / 64) * 512);
         for (int r = threadIdx.x; r <= nrow; r += blockDim.x) s_cnt[r] = 0;
         SYNC();
         for (int i = threadIdx.x; i < Nr; i += blockDim.x)
@@ -2675,140 +2711,218 @@ __global__ __launch_bounds__(ST_NT) void k_stereo(OrbGeom g, StereoSide SL, Ster
         SYNC();
     }
     const int maxspan = s_maxspan;
-    float* uR_out = uright + (size_t)f * g.kp_cap;
-    float* dp_out = depth + (size_t)f * g.kp_cap;
-    int* sd_out = sdist + (size_t)f * g.kp_cap;
     const float mb = sa.bf / sa.fx;   // intended mb = mbf/fx (the reference reads it uninitialised)
     const float minZ = mb, minD = 0.f, maxD = sa.bf / minZ;
-    const int iend = min(N, i0 + sa.lk);
-    // the first keypoint of each wave is static; later ones come from a block counter, so waves whose
-    // keypoints scan few candidates take more of them and the block ends with its work, not with its
-    // slowest wave's fixed share (253 -> 236 us per 512 frames; r03_kernel_ab.txt item 29)
-    for (int iL = i0 + wave; iL < iend;) {
-        float outU = -1.0f, outD = -1.0f;
-        int outS = -1;
-        const OrbKeyPoint kpL = kL[iL];
-        const int levelL = kpL.octave;
-        const float vL = kpL.y, uL = kpL.x;
-        const int row = (int)vL;
-        const float minU = uL - maxD, maxU = uL - minD;
-        uint32_t dl[8];
+    const int nk = min(N, i0 + sa.lk) - i0;   // left keypoints of this block: 1 .. sa.lk
+    // lane group `grp` of wave `wave` is unit gid of 64: a round's keypoints (items) are dealt one per
+    // wave first, so a partial round spreads over all waves
+    const int grp = lane >> 4, l16 = lane & 15;
+    const int gid = grp * (ST_NT / 64) + wave;
+    uint4* s_item = (uint4*)s_scr;   // {uL, scaled uR0, first window row, key | level << 16}
+    // ---- phase A: match ----
+    {
+        const int roundsA = (nk + 63) >> 6;
+        int kn = i0 + min(gid, nk - 1);
+        float nx = kL[kn].x, ny = kL[kn].y;
+        int noct = kL[kn].octave;
+        uint32_t ndl[8];
 #pragma unroll
-        for (int k = 0; k < 8; k++) dl[k] = dL[(size_t)iL * 8 + k];
-        int bestKey = 0x7fffffff;   // (dist << 16) | iR: the first best in iR order
-        bool anyCand = false;
-        // records whose band can contain `row`: minr in [row - maxspan, row]
-        auto lower = [&](uint32_t t) {
-            int lo = 0, hi = Nr;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (s_key[mid] < t) lo = mid + 1; else hi = mid;
-            }
-            return lo;
-        };
-        const bool tab = row - maxspan >= -ST_ROFF && row + 1 < g.height + ST_ROFF;   // wave-uniform
-        const int jlo = tab ? (int)s_rowst[row - maxspan + ST_ROFF] : lower((uint32_t)max(row - maxspan + 1024, 0) << 16);
-        const int jhi = tab ? (int)s_rowst[row + 1 + ST_ROFF] : lower((uint32_t)max(row + 1 + 1024, 0) << 16);
-        for (int j = jlo + lane; j < jhi; j += 64) {
-            const int iR = (int)(s_key[j] & 0xFFFFu);
-            const RightRec rr = s_rec[iR];
-            if (rr.minr <= row && row <= rr.maxr) {
-                anyCand = true;
-                if (rr.oct >= levelL - 1 && rr.oct <= levelL + 1 && rr.x >= minU && rr.x <= maxU) {
-                    const int dist = hamming32(dl, s_descR + 8 * iR);
-                    bestKey = min(bestKey, (dist << 16) | iR);
+        for (int k = 0; k < 8; k++) ndl[k] = dL[(size_t)kn * 8 + k];
+        for (int t = 0; t < roundsA; t++) {
+            const int key = gid + 64 * t;   // block-relative left keypoint
+            const bool kvalid = key < nk;
+            const float uL = nx, vL = ny;
+            const int levelL = noct;
+            uint32_t dl[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) dl[k] = ndl[k];
+            // the next round's record and descriptor fly during this round's scan (past the end:
+            // the block's last keypoint again)
+            kn = i0 + min(key + 64, nk - 1);
+            nx = kL[kn].x;
+            ny = kL[kn].y;
+            noct = kL[kn].octave;
+#pragma unroll
+            for (int k = 0; k < 8; k++) ndl[k] = dL[(size_t)kn * 8 + k];
+            const int row = (int)vL;
+            const float minU = uL - maxD, maxU = uL - minD;
+            int bestKey = 0x7fffffff;   // (dist << 16) | iR: the first best in iR order
+            bool anyCand = false;
+            // records whose band can contain `row`: minr in [row - maxspan, row]
+            auto lower = [&](uint32_t tk) {
+                int lo = 0, hi = Nr;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (s_key[mid] < tk) lo = mid + 1; else hi = mid;
+                }
+                return lo;
+            };
+            int jlo = 0, jhi = 0;
+            if (kvalid) {
+                if (row - maxspan >= -ST_ROFF && row + 1 < g.height + ST_ROFF) {
+                    jlo = (int)s_rowst[row - maxspan + ST_ROFF];
+                    jhi = (int)s_rowst[row + 1 + ST_ROFF];
+                } else {
+                    jlo = lower((uint32_t)max(row - maxspan + 1024, 0) << 16);
+                    jhi = lower((uint32_t)max(row + 1 + 1024, 0) << 16);
                 }
             }
-        }
-        bestKey = wave_min_dpp(bestKey);
-        const bool cand = __any(anyCand) && !(maxU < 0);
-        const int bestDist = bestKey == 0x7fffffff ? 100 : min(100, bestKey >> 16);
-        if (cand && bestDist < 75) {   // thOrbDist = (TH_HIGH + TH_LOW) / 2
-            const int bestIdxR = bestKey & 0xffff;
-            const float uR0 = s_rec[bestIdxR].x;
-            const float sf = g.lv[levelL].inv_scale;
-            const float scaleduL = roundf(kpL.x * sf);
-            const float scaledvL = roundf(kpL.y * sf);
-            const float scaleduR0 = roundf(uR0 * sf);
-            const int w = 5, Lr = 5;
-            const float iniu = scaleduR0 + Lr - w;
-            const float endu = scaleduR0 + Lr + w + 1;
-            const OrbLevel& LV = g.lv[levelL];
-            if (!(iniu < 0 || endu >= LV.w)) {
-                int pL, pR;
-                gptr_u8 IL = level_base(SL.imgs, SL.in_pitch, SL.pyr, SL.pyr_stride, g, bL, levelL, &pL);
-                gptr_u8 IR = level_base(SR.imgs, SR.in_pitch, SR.pyr, SR.pyr_stride, g, bR, levelL, &pR);
-                const int r0 = (int)(scaledvL - w), c0L = (int)(scaleduL - w), c0R = (int)(scaleduR0 - Lr - w);
-                // stage the IL 11x11 and IR 11x21 windows as dword rows (IL: 3 dwords, byte 11
-                // zeroed; IR: 6 dwords): lanes 0-10 load a left row, 11-21 a right row with aligned
-                // dword loads (the windows lie >= 6 px inside the level, so the <= 3-byte over-reads
-                // stay inside the image) realigned by v_alignbyte
-                uint32_t* s_wl = (uint32_t*)s_win;          // [11][3]
-                uint32_t* s_wr = (uint32_t*)s_win + 33;     // [11][6]
-                if (lane < 22) {
-                    const bool left = lane < 11;
-                    const int yy = left ? lane : lane - 11;
-                    gptr_u8 rp = left ? IL + (size_t)(r0 + yy) * pL + c0L : IR + (size_t)(r0 + yy) * pR + c0R;
-                    const uint32_t sh = (uint32_t)((uintptr_t)rp & 3);
-                    gptr_u32 ap = (gptr_u32)(rp - sh);
-                    uint32_t w[7];
-#pragma unroll
-                    for (int k = 0; k < 7; k++) w[k] = (left && k >= 4) ? 0u : ap[k];
-                    if (left) {
-#pragma unroll
-                        for (int k = 0; k < 3; k++) {
-                            uint32_t o = __builtin_amdgcn_alignbyte(w[k + 1], w[k], sh);
-                            if (k == 2) o &= 0x00FFFFFFu;
-                            s_wl[yy * 3 + k] = o;
-                        }
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < 6; k++) s_wr[yy * 6 + k] = __builtin_amdgcn_alignbyte(w[k + 1], w[k], sh);
+            for (int j = jlo + l16; j < jhi; j += 16) {
+                const int iR = (int)(s_key[j] & 0xFFFFu);
+                const RightRec rr = s_rec[iR];
+                if (rr.minr <= row && row <= rr.maxr) {
+                    anyCand = true;
+                    if (rr.oct >= levelL - 1 && rr.oct <= levelL + 1 && rr.x >= minU && rr.x <= maxU) {
+                        const int dist = hamming32(dl, s_descR + 8 * iR);
+                        bestKey = min(bestKey, (dist << 16) | iR);
                     }
                 }
-                // lanes: (shift inc, window row) pairs -> row SAD over 11 columns, 3 v_sad_u8
-                for (int pidx = lane; pidx < 121; pidx += 64) {
-                    const int inc = pidx / 11, yy = pidx - inc * 11;
-                    const uint32_t* rr = s_wr + yy * 6 + (inc >> 2);
-                    const uint32_t ish = (uint32_t)(inc & 3);
-                    const uint32_t r0w = __builtin_amdgcn_alignbyte(rr[1], rr[0], ish);
-                    const uint32_t r1w = __builtin_amdgcn_alignbyte(rr[2], rr[1], ish);
-                    const uint32_t r2w = __builtin_amdgcn_alignbyte(rr[3], rr[2], ish) & 0x00FFFFFFu;
-                    const uint32_t* ll = s_wl + yy * 3;
-                    s_part[pidx] = (int)__builtin_amdgcn_sad_u8(
-                        ll[2], r2w, __builtin_amdgcn_sad_u8(ll[1], r1w, __builtin_amdgcn_sad_u8(ll[0], r0w, 0u)));
+            }
+            bestKey = row16_min_dpp(bestKey);   // lane 15 of the group
+            const bool cand = ((__ballot(anyCand) >> (16 * grp)) & 0xFFFFull) != 0 && !(maxU < 0);
+            const int bestDist = bestKey == 0x7fffffff ? 100 : min(100, bestKey >> 16);
+            bool emit = false;
+            uint4 item = make_uint4(0u, 0u, 0u, 0u);
+            if (l16 == 15 && kvalid && cand && bestDist < 75) {   // thOrbDist = (TH_HIGH + TH_LOW) / 2
+                const int bestIdxR = bestKey & 0xffff;
+                const float uR0 = s_rec[bestIdxR].x;
+                const StLevel LV = s_lv[levelL];
+                const float sf = LV.inv_scale;
+                const float scaledvL = roundf(vL * sf);
+                const float scaleduR0 = roundf(uR0 * sf);
+                const int w = 5, Lr = 5;
+                const float iniu = scaleduR0 + Lr - w;
+                const float endu = scaleduR0 + Lr + w + 1;
+                if (!(iniu < 0 || endu >= LV.w)) {
+                    emit = true;
+                    item = make_uint4(__float_as_uint(uL), __float_as_uint(scaleduR0), (uint32_t)(int)(scaledvL - w),
+                                      (uint32_t)key | ((uint32_t)levelL << 16));
                 }
-                int dsum = 0;
-                if (lane < 11)
-                    for (int yy = 0; yy < 11; yy++) dsum += s_part[lane * 11 + yy];
-                float dists[11];
+            }
+            const unsigned long long em = __ballot(emit);
+            if (em) {   // wave-uniform
+                int base = 0;
+                if (lane == 0) base = atomicAdd(&s_nitem, __popcll(em));
+                base = __builtin_amdgcn_readfirstlane(base);
+                if (emit) s_item[base + lanes_below(em)] = item;
+            }
+        }
+    }
+    SYNC();
+    // the right descriptors are dead: their space takes the block's results
+    const int M = s_nitem;
+    float* s_resU = (float*)s_descR;
+    float* s_resD = s_resU + nk;
+    int* s_resS = (int*)(s_resD + nk);
+    for (int i = threadIdx.x; i < nk; i += blockDim.x) { s_resU[i] = -1.0f; s_resD[i] = -1.0f; s_resS[i] = -1; }
+    SYNC();
+    // ---- phase B: SAD refinement of the work items ----
+    if (M > 0) {   // block-uniform
+        const gptr_u8 IL0 = as_global(SL.imgs[bL]), IR0 = as_global(SR.imgs[bR]);
+        const gptr_u8 PL = as_global(SL.pyr + (size_t)bL * SL.pyr_stride), PR = as_global(SR.pyr + (size_t)bR * SR.pyr_stride);
+        const int yy = min(l16, 10);   // lanes 11-15 of a group repeat row 10's addresses
+        // row yy of item `it`: IL 11 bytes (4 aligned dwords), IR 21 bytes (7 aligned dwords); the
+        // windows lie >= 6 px inside the level, so the <= 3-byte over-reads stay inside the image
+        auto fetch = [&](const uint4 it, uint32_t (&wl)[4], uint32_t (&wr)[7]) -> uint32_t {
+            const int lvl = (int)(it.w >> 16);
+            const StLevel LV = s_lv[lvl];
+            const float uL = __uint_as_float(it.x), scaleduR0 = __uint_as_float(it.y);
+            const int w = 5, Lr = 5;
+            const float scaleduL = roundf(uL * LV.inv_scale);
+            const int r0 = (int)it.z, c0L = (int)(scaleduL - w), c0R = (int)(scaleduR0 - Lr - w);
+            const int pL = lvl == 0 ? SL.in_pitch : LV.pitch, pR = lvl == 0 ? SR.in_pitch : LV.pitch;
+            const gptr_u8 IL = lvl == 0 ? IL0 : PL + LV.pyr_off;
+            const gptr_u8 IR = lvl == 0 ? IR0 : PR + LV.pyr_off;
+            const gptr_u8 rl = IL + (size_t)(r0 + yy) * pL + c0L;
+            const gptr_u8 rr = IR + (size_t)(r0 + yy) * pR + c0R;
+            const uint32_t shl = (uint32_t)((uintptr_t)rl & 3), shr = (uint32_t)((uintptr_t)rr & 3);
+            const gptr_u32 al = (gptr_u32)(rl - shl), ar = (gptr_u32)(rr - shr);
+#pragma unroll
+            for (int k = 0; k < 4; k++) wl[k] = al[k];
+#pragma unroll
+            for (int k = 0; k < 7; k++) wr[k] = ar[k];
+            return shl | (shr << 2);
+        };
+        const int roundsB = (M + 63) >> 6;
+        uint4 nit = s_item[min(gid, M - 1)];
+        uint32_t nwl[4], nwr[7];
+        uint32_t nsh = fetch(nit, nwl, nwr);
+        for (int t = 0; t < roundsB; t++) {
+            const int idx = gid + 64 * t;
+            const uint4 it = nit;
+            const uint32_t shl = nsh & 3u, shr = nsh >> 2;
+            uint32_t wl[4], wr[7];
+#pragma unroll
+            for (int k = 0; k < 4; k++) wl[k] = nwl[k];
+#pragma unroll
+            for (int k = 0; k < 7; k++) wr[k] = nwr[k];
+            // the next round's window rows fly during this round's SADs (past the end of the list:
+            // its last item again)
+            nit = s_item[min(idx + 64, M - 1)];
+            nsh = fetch(nit, nwl, nwr);
+            // realign: IL row as 3 dwords (byte 11 zeroed), IR row as 6 dwords
+            uint32_t ll[3], rw[6];
+#pragma unroll
+            for (int k = 0; k < 3; k++) ll[k] = __builtin_amdgcn_alignbyte(wl[k + 1], wl[k], shl);
+            ll[2] &= 0x00FFFFFFu;
+#pragma unroll
+            for (int k = 0; k < 6; k++) rw[k] = __builtin_amdgcn_alignbyte(wr[k + 1], wr[k], shr);
+            // row SAD over 11 columns for each of the 11 shifts (3 v_sad_u8), summed over the rows
+            const bool rowlane = l16 < 11;
+            uint32_t dsum[11];
+#pragma unroll
+            for (int inc = 0; inc < 11; inc++) {
+                const int q = inc >> 2;
+                const uint32_t ish = (uint32_t)(inc & 3);
+                const uint32_t r0w = __builtin_amdgcn_alignbyte(rw[q + 1], rw[q], ish);
+                const uint32_t r1w = __builtin_amdgcn_alignbyte(rw[q + 2], rw[q + 1], ish);
+                const uint32_t r2w = __builtin_amdgcn_alignbyte(q + 3 < 6 ? rw[q + 3] : 0u, rw[q + 2], ish) & 0x00FFFFFFu;
+                const uint32_t sad = __builtin_amdgcn_sad_u8(
+                    ll[2], r2w, __builtin_amdgcn_sad_u8(ll[1], r1w, __builtin_amdgcn_sad_u8(ll[0], r0w, 0u)));
+                dsum[inc] = row16_sum_dpp(rowlane ? sad : 0u);   // lane 15 of the group
+            }
+            if (l16 == 15 && idx < M) {
+                const int Lr = 5;
+                const int lvl = (int)(it.w >> 16), key = (int)(it.w & 0xFFFFu);
+                const float uL = __uint_as_float(it.x), scaleduR0 = __uint_as_float(it.y);
+                const float scale = s_lv[lvl].scale;
+                float dist1 = 0.f, dist2 = 0.f, dist3 = 0.f;   // the distances around the best shift
                 int bestD = 0x7fffffff, bestinc = 0;
 #pragma unroll
                 for (int k = 0; k < 11; k++) {
-                    const float dist = (float)__builtin_amdgcn_readlane(dsum, k);   // cv::norm(NORM_L1) of shift k - Lr
-                    dists[k] = dist;
-                    if (dist < (float)bestD) { bestD = (int)dist; bestinc = k - Lr; }
+                    const float dist = (float)(int)dsum[k];   // cv::norm(NORM_L1) of shift k - Lr
+                    if (dist < (float)bestD) {
+                        bestD = (int)dist;
+                        bestinc = k - Lr;
+                        dist1 = k > 0 ? (float)(int)dsum[k > 0 ? k - 1 : 0] : 0.f;
+                        dist2 = dist;
+                        dist3 = k < 10 ? (float)(int)dsum[k < 10 ? k + 1 : 10] : 0.f;
+                    }
                 }
                 if (!(bestinc == -Lr || bestinc == Lr)) {
-                    const float dist1 = dists[Lr + bestinc - 1], dist2 = dists[Lr + bestinc], dist3 = dists[Lr + bestinc + 1];
                     const float deltaR = (dist1 - dist3) / (2.0f * (dist1 + dist3 - 2.0f * dist2));
                     if (!(deltaR < -1 || deltaR > 1)) {
-                        float bestuR = LV.scale * ((float)scaleduR0 + (float)bestinc + deltaR);
+                        float bestuR = scale * ((float)scaleduR0 + (float)bestinc + deltaR);
                         float disparity = (uL - bestuR);
                         if (disparity >= minD && disparity < maxD) {
                             if (disparity <= 0) { disparity = (float)0.01; bestuR = (float)((double)uL - 0.01); }
-                            outD = sa.bf / disparity;
-                            outU = bestuR;
-                            outS = bestD;
+                            s_resD[key] = sa.bf / disparity;
+                            s_resU[key] = bestuR;
+                            s_resS[key] = bestD;
                         }
                     }
                 }
             }
         }
-        if (lane == 0) { uR_out[iL] = outU; dp_out[iL] = outD; sd_out[iL] = outS; }
-        int nx = 0;
-        if (lane == 0) nx = atomicAdd(&s_next, 1);
-        iL = i0 + __builtin_amdgcn_readfirstlane(nx);
+    }
+    SYNC();
+    float* uR_out = uright + (size_t)f * g.kp_cap + i0;
+    float* dp_out = depth + (size_t)f * g.kp_cap + i0;
+    int* sd_out = sdist + (size_t)f * g.kp_cap + i0;
+    for (int i = threadIdx.x; i < nk; i += blockDim.x) {
+        uR_out[i] = s_resU[i];
+        dp_out[i] = s_resD[i];
+        sd_out[i] = s_resS[i];
     }
 }
 
