@@ -1088,6 +1088,7 @@ int orbfe_matcher_last_sim3_passes(void);
  * 5 = how the last batch built `level`, int32[4] {one-launch pyramid tiles (0: the geometry does not
  *     fit it), builder (0 the caller's image, 1 one-launch pyramid, 2 row-streamed resize, 3 tiled
  *     resize), the level fits the row-streamed resize, pitch and every pointer 4-byte aligned}.
+ * 6 = resize geometry of `level`, int32[6] {rz_rows, rz_cols, rs_rows as launched (0: not row-streamed), simd_end, xmax, pitch}.
  * Returns the element count. */
 int orbfe_debug_copy(orbfe_extractor* h, int what, int image, int level, void* dst, int cap_bytes);
 

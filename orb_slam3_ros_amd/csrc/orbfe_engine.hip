@@ -149,6 +149,7 @@ struct orbfe_extractor {
     int last_nimg = 0, last_pitch = 0;
     // how the last batch built its pyramid (orbfe_debug_copy what = 5): 1 k_pyramid, 2 k_resize_s, 3 k_resize
     int last_al0 = 0, last_builder[ORBFE_MAX_LEVELS] = {};
+    int last_rs_rows[ORBFE_MAX_LEVELS] = {};   // k_resize_s rows per wave as launched (what = 6); 0: another builder
     // extraction counter (every run_batch) and the matcher view of the last orbfe_frame_stereo call:
     // its id, left keypoint count, and the scale factors on the device (orbfe_frame_device_view)
     uint64_t frame_id = 0, fs_id = 0;
@@ -677,6 +678,7 @@ static int run_batch(orbfe_extractor* h, int B, const uint8_t* const* host_ptrs,
         const bool fused_pyr = h->pt_n > 0 && !h->no_fused_pyramid && (small || h->fused_pyramid_batch);
         h->last_al0 = al0 ? 1 : 0;
         for (int l = 1; l < g.nlevels; l++) h->last_builder[l] = fused_pyr ? 1 : (g.lv[l].rs_ok && (l > 1 || al0)) ? 2 : 3;
+        for (int l = 1; l < g.nlevels; l++) h->last_rs_rows[l] = h->last_builder[l] == 2 ? gr.lv[l].rs_rows : 0;
         if (fused_pyr)
             hipLaunchKernelGGL(k_pyramid, dim3(h->pt_n, B), dim3(PYR_NT), h->pt_lds, s, P, pitch, h->d_pyr, g.pyr_bytes, g,
                                h->d_ptile, h->pt_stride, h->pt_cap, al0 ? 1 : 0);
@@ -1450,6 +1452,13 @@ int orbfe_debug_copy(orbfe_extractor* h, int what, int image, int level, void* d
         const int path[4] = {h->pt_n, level ? h->last_builder[level] : 0, L.rs_ok, h->last_al0};
         memcpy(dst, path, 16);
         return 4;
+    }
+    else if (what == 6) {
+        if (cap_bytes < 24) return ORBFE_E_CAPACITY;
+        const int geo[6] = {level ? L.rz_rows : 0, level ? L.rz_cols : 0, level ? h->last_rs_rows[level] : 0,
+                            level ? L.simd_end : 0, level ? L.xmax : 0, level ? L.pitch : h->last_pitch};
+        memcpy(dst, geo, 24);
+        return 6;
     }
     else if (what == 4) {
         if (!h->d_oct_ts) return 0;

@@ -57,6 +57,7 @@ def _device_batch(imgs, pitch, offset, pad, seed=0):
     256-byte aligned allocation; every byte that is not a pixel holds the padding pattern."""
     import torch
     n = len(imgs)
+    H, W = imgs[0].shape
     total = offset + n * H * pitch + 64
     if pad == "random":
         host = np.random.default_rng(1000 + seed).integers(0, 256, total, dtype=np.uint8)
@@ -72,12 +73,14 @@ def _device_batch(imgs, pitch, offset, pad, seed=0):
 class _Batch:
     """One extractor handle with caller-owned batch outputs."""
 
-    def __init__(self, nimg, device):
+    def __init__(self, nimg, device, w=W, h=H, nfeat=NFEAT, scale=1.2, nlevels=NLEVELS, lanes=None, lap=LAP):
         import torch
         from orb_slam3_ros_amd.extractor import ORBextractor
-        self.ext = ORBextractor(NFEAT, 1.2, NLEVELS, 20, 7)
-        self.n = nimg
-        self.cap = self.ext.capacity(W, H)
+        self.ext = ORBextractor(nfeat, scale, nlevels, 20, 7)
+        if lanes is not None:
+            self.ext.set_opencv_model(lanes, 0)
+        self.n, self.w, self.h, self.nlevels, self.lap = nimg, w, h, nlevels, lap
+        self.cap = self.ext.capacity(w, h)
         self.kps = torch.zeros((nimg, self.cap, 7), dtype=torch.int32, device=device)
         self.desc = torch.zeros((nimg, self.cap, 32), dtype=torch.uint8, device=device)
         self.cnt = torch.zeros((nimg, 2), dtype=torch.int32, device=device)
@@ -88,8 +91,8 @@ class _Batch:
     def run(self, ptrs, pitch):
         import torch
         arr = (ctypes.c_void_p * self.n)(*ptrs)
-        rc = self.ext._lib.orbfe_extract_batch(self.ext.handle, self.n, arr, W, H, pitch, LAP[0], LAP[1], None)
-        assert rc == 0, f"orbfe_extract_batch refused {self.n} images of {W}x{H}, pitch {pitch}: {rc}"
+        rc = self.ext._lib.orbfe_extract_batch(self.ext.handle, self.n, arr, self.w, self.h, pitch, self.lap[0], self.lap[1], None)
+        assert rc == 0, f"orbfe_extract_batch refused {self.n} images of {self.w}x{self.h}, pitch {pitch}: {rc}"
         torch.cuda.synchronize()
         cnt = self.cnt.cpu().numpy()
         kps, desc = self.kps.cpu().numpy(), self.desc.cpu().numpy()
@@ -99,7 +102,7 @@ class _Batch:
         """Per level >= 1 of the last batch: (builder, fits the row-streamed resize), and whether the
         one-launch pyramid takes this geometry and the input counted as 4-byte aligned."""
         out, tiles, al0 = [], 0, 0
-        for l in range(1, NLEVELS):
+        for l in range(1, self.nlevels):
             info = np.zeros(4, np.int32)
             assert self.ext._lib.orbfe_debug_copy(self.ext.handle, 5, 0, l, info.ctypes.data, 16) == 4
             tiles, al0 = int(info[0]), int(info[3])
