@@ -2212,8 +2212,14 @@ __device__ __forceinline__ float fast_atan2_dev(float y, float x) {
 #define DP_WAVE_LDS 5600   // >= 43*48 + 22*40*4, multiple of 16
 #define DP_ND (DP_N * (DP_RAW_S / 4))   // 516 patch dwords
 // One output slot of an image (wave-uniform): level, key, output index and the patch geometry.
+// A border slot (patch outside the level, or too close to its right edge for the interior window) of
+// a dword-aligned level is staged from the same three 16-byte loads per lane: rows reflect in the load
+// address, and the 48-byte window starts at gx0 clamped into the row, [0, pitch - 48]. Patch column 0
+// is window byte 4 sd + sh (sd < 0 on the left edge); patch columns [0, nl) and [cr, 43) lie outside
+// the level and are mirrored from the staged ones in LDS.
 struct DescSlot {
     int valid, l, x, y, interior, pitch, gx0, sh;
+    int border;   // 0, or 1 | sd + 2 << 1 | nl << 4 | 43 - cr << 8 | level height << 12
     uint32_t key;
     size_t o;
     gptr_u8 im;
@@ -2271,8 +2277,24 @@ __device__ __forceinline__ DescSlot desc_slot(const uint8_t* const* imgs, int in
     const int px0 = d.x - DP_R, py0 = d.y - DP_R;
     d.gx0 = px0 & ~3;
     d.sh = px0 - d.gx0;
-    d.interior = px0 >= 0 && py0 >= 0 && py0 + DP_N <= L.h && d.gx0 + DP_RAW_S + 4 <= L.w && (d.pitch & 3) == 0 &&
-                 ((((uintptr_t)d.im) & 3) == 0);
+    const bool aligned = (d.pitch & 3) == 0 && ((((uintptr_t)d.im) & 3) == 0);
+    d.interior = px0 >= 0 && py0 >= 0 && py0 + DP_N <= L.h && d.gx0 + DP_RAW_S + 4 <= L.w && aligned;
+    d.border = 0;
+    if (!d.interior && aligned && d.pitch >= DP_RAW_S) {
+        const int ws = min(max(d.gx0, 0), d.pitch - DP_RAW_S);   // a multiple of 4; ws + 48 <= pitch
+        const int s = px0 - ws;
+        const int nl = max(-px0, 0), cr = min(L.w - px0, DP_N);
+        // every row reflects once into [0, h); the columns mirrored from, (nl, 2 nl] and
+        // [2 cr - 44, cr - 2], are columns of the level, and the level's columns [nl, cr) of the
+        // patch are window bytes [nl + s, cr + s) of [0, 48). Anything else (a level narrower or
+        // lower than a patch reflects into) keeps the byte loop.
+        if (py0 > -L.h && py0 + DP_N < 2 * L.h && nl <= 8 && DP_N - cr <= 8 && 2 * nl < cr &&
+            2 * cr - DP_N - 1 >= nl && nl + s >= 0 && cr + s <= DP_RAW_S) {
+            d.border = 1 | (((s >> 2) + 2) << 1) | (nl << 4) | ((DP_N - cr) << 8) | (L.h << 12);
+            d.gx0 = ws;
+            d.sh = s & 3;
+        }
+    }
     return d;
 }
 // Patch of an interior slot as 16-byte chunks of the 48-byte rows from gx0: lane = 3 r + k (k =
@@ -2280,6 +2302,16 @@ __device__ __forceinline__ DescSlot desc_slot(const uint8_t* const* imgs, int in
 // 42, not stored). Three dwordx4 loads per lane instead of 18 dword loads.
 __device__ __forceinline__ void desc_load(const DescSlot& d, int lane, orbfe_u32x4 (&q)[3]) {
     const int r0 = small_div(lane, 3), k = lane - 3 * r0;
+    if (d.border) {
+        // the same chunks of the clamped window; the row index reflects into the level
+        gptr_u8 b0 = d.im + d.gx0 + 16 * k;
+#pragma unroll
+        for (int u = 0; u < 3; u++) {
+            const uint32_t row = (uint32_t)reflect101(d.y - DP_R + min(r0 + 21 * u, DP_N - 1), d.border >> 12);
+            q[u] = *(const ORBFE_GLOBAL orbfe_u32x4*)(b0 + __umul24(row, (uint32_t)d.pitch));
+        }
+        return;
+    }
     gptr_u8 b0 = d.im + (size_t)(d.y - DP_R) * d.pitch + d.gx0 + 16 * k;
 #pragma unroll
     for (int u = 0; u < 3; u++) {
@@ -2301,6 +2333,40 @@ __device__ __forceinline__ void desc_stage(uint8_t* raw, int lane, const orbfe_u
         w.z = __builtin_amdgcn_alignbyte(q[u].w, q[u].z, (uint32_t)sh);
         w.w = __builtin_amdgcn_alignbyte(nx, q[u].w, (uint32_t)sh);
         if (lane < 63 && r0 + 21 * u < DP_N) *(uint4*)(raw + (r0 + 21 * u) * DP_RAW_S + 16 * k) = w;
+    }
+}
+// The chunks of a border slot: patch dword p of a row is window bytes 4 (p + sd) + sh .. + 3, so a
+// lane's chunk realigned by sh gives patch dwords 4 k - sd .. 4 k - sd + 3 (the last with the next
+// lane's first dword, as above) and, with the previous lane's last dword (DPP wave_shr), dword
+// 4 k - sd - 1: on the left edge that one holds the level's first columns. Dwords outside the row are
+// dropped; bytes that come from a neighbouring row's chunk only land on columns outside the level or
+// past column 42. After the wave's stores lane r mirrors row r's outside columns from the row itself.
+__device__ __forceinline__ void desc_stage_border(uint8_t* raw, int lane, const orbfe_u32x4 (&q)[3], const DescSlot& d) {
+    const int r0 = small_div(lane, 3), k = lane - 3 * r0;
+    const int sd = ((d.border >> 1) & 7) - 2, nl = (d.border >> 4) & 15, cr = DP_N - ((d.border >> 8) & 15);
+    const int p0 = 4 * k - sd - 1;
+#pragma unroll
+    for (int u = 0; u < 3; u++) {
+        const uint32_t nx = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)q[u].x, 0x130, 0xf, 0xf, false);
+        const uint32_t pv = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)q[u].w, 0x138, 0xf, 0xf, false);
+        uint32_t w[5];
+        w[0] = __builtin_amdgcn_alignbyte(q[u].x, pv, (uint32_t)d.sh);
+        w[1] = __builtin_amdgcn_alignbyte(q[u].y, q[u].x, (uint32_t)d.sh);
+        w[2] = __builtin_amdgcn_alignbyte(q[u].z, q[u].y, (uint32_t)d.sh);
+        w[3] = __builtin_amdgcn_alignbyte(q[u].w, q[u].z, (uint32_t)d.sh);
+        w[4] = __builtin_amdgcn_alignbyte(nx, q[u].w, (uint32_t)d.sh);
+        if (lane < 63 && r0 + 21 * u < DP_N) {
+            uint32_t* rp = (uint32_t*)(raw + (r0 + 21 * u) * DP_RAW_S);
+#pragma unroll
+            for (int i = 0; i < 5; i++)
+                if ((unsigned)(p0 + i) < DP_RAW_S / 4) rp[p0 + i] = w[i];
+        }
+    }
+    WAVE_SYNC();
+    if (lane < DP_N) {
+        uint8_t* rr = raw + lane * DP_RAW_S;
+        for (int c = 0; c < nl; c++) rr[c] = rr[2 * nl - c];
+        for (int c = cr; c < DP_N; c++) rr[c] = rr[2 * cr - 2 - c];
     }
 }
 // IC_Angle + Gaussian + rBRIEF of one slot whose raw patch is staged in `raw`; writes the
@@ -2461,7 +2527,7 @@ __device__ __forceinline__ void describe_one(const DescSlot& d, const OrbGeom& g
 // resident per XCD overflow its L2: hit rate 0.84 -> 0.70) and left the full step unchanged
 // (r03_kernel_ab.txt item 19)
 #define DP_KPW 4
-// 6 waves per SIMD: 79 VGPRs, no spill since the pattern is held as f16 (at 5 waves without a spill
+// 6 waves per SIMD: 78 VGPRs, no spill since the pattern is held as f16 (at 5 waves without a spill
 // or 6 with one the kernel measured slower or equal: 1 slot / 4 slots at 5, 6, 7 waves, 2, 3 and 8
 // slots, tools/gpu_variants_trace.sh; DESIGN.md §7d, profiles/r03_kernel_ab.txt items 18-19)
 #ifndef DP_WAVES
@@ -2506,19 +2572,23 @@ __global__ __launch_bounds__(64 * DP_WPB) DP_ATTR void k_describe(const uint8_t*
     int lvl = 0;
     DescSlot cur = desc_slot(imgs, in_pitch, pyr, pyr_stride, g, di, kv, rv, 0, &lvl, b, flat0);
     orbfe_u32x4 pq[3];
-    if (cur.valid && cur.interior) desc_load(cur, lane, pq);
+    if (cur.valid && (cur.interior | cur.border)) desc_load(cur, lane, pq);
 #pragma unroll
     for (int j = 0; j < KPW; j++) {
         // ---- stage the raw patch: raw[r][c] = level(y - 21 + r, x - 21 + c), reflect-101 outside ----
         if (cur.valid) {
             if (cur.interior) {
                 desc_stage(raw, lane, pq, cur.sh);
+            } else if (cur.border) {
+                desc_stage_border(raw, lane, pq, cur);
             } else {
+                // levels whose base or pitch is no multiple of 4 (and patches a small level reflects twice)
                 const OrbLevel& L = g.lv[cur.l];
                 const int px0 = cur.x - DP_R, py0 = cur.y - DP_R;
                 for (int it = lane; it < DP_N * DP_N; it += 64) {
                     const int r = it / DP_N, c = it - r * DP_N;
-                    raw[r * DP_RAW_S + c] = cur.im[(size_t)reflect101(py0 + r, L.h) * cur.pitch + reflect101(px0 + c, L.w)];
+                    raw[r * DP_RAW_S + c] = cur.im[__umul24((uint32_t)reflect101(py0 + r, L.h), (uint32_t)cur.pitch) +
+                                                   (uint32_t)reflect101(px0 + c, L.w)];
                 }
             }
         }
@@ -2528,7 +2598,7 @@ __global__ __launch_bounds__(64 * DP_WPB) DP_ATTR void k_describe(const uint8_t*
         nxt.valid = 0;
         if (j + 1 < KPW) {
             nxt = desc_slot(imgs, in_pitch, pyr, pyr_stride, g, di, kv, rv, j + 1, &lvl, b, flat0 + j + 1);
-            if (nxt.valid && nxt.interior) desc_load(nxt, lane, pq);
+            if (nxt.valid && (nxt.interior | nxt.border)) desc_load(nxt, lane, pq);
         }
         if (cur.valid) describe_one(cur, g, raw, rowp, pat, lane, kps, desc, bk, s_icm);
         WAVE_SYNC();   // the patch area is restaged for the next slot
