@@ -45,35 +45,6 @@ __global__ __launch_bounds__(MT_NT) void k_bow_kfkf(const int* pairs, int npairs
     }
 }
 
-__global__ __launch_bounds__(1024) void k_bow_kfkf_commit(const OrbKeyPoint* k1, const OrbKeyPoint* k2, int n1,
-                                                          const int32_t* mp2, int checkOri, const int* out_idx,
-                                                          int* out12, int* result) {
-    __shared__ int s_hist[MT_HISTO];
-    __shared__ unsigned s_keep;
-    __shared__ int s_n;
-    if (threadIdx.x < MT_HISTO) s_hist[threadIdx.x] = 0;
-    if (threadIdx.x == 0) s_n = 0;
-    SYNC();
-    for (int i = threadIdx.x; i < n1; i += blockDim.x) {
-        const int j = out_idx[i];
-        if (j >= 0 && checkOri) atomicAdd(&s_hist[mt_rot_bin(k1[i].angle, k2[j].angle)], 1);
-    }
-    SYNC();
-    if (threadIdx.x == 0) s_keep = checkOri ? mt_three_maxima_keep(s_hist) : 0xFFFFFFFFu;
-    SYNC();
-    int cnt = 0;
-    for (int i = threadIdx.x; i < n1; i += blockDim.x) {
-        const int j = out_idx[i];
-        int o = -1;
-        if (j >= 0 && (!checkOri || ((s_keep >> mt_rot_bin(k1[i].angle, k2[j].angle)) & 1u))) o = mp2 ? mp2[j] : j;
-        out12[i] = o;
-        cnt += o >= 0 ? 1 : 0;
-    }
-    atomicAdd(&s_n, cnt);
-    SYNC();
-    if (threadIdx.x == 0) result[0] = s_n;
-}
-
 #define DD_MAXN 2048   // descriptors per point accepted by the API
 #define DD_LDS_N 256   // descriptors per point staged in LDS (larger points read L2-resident global rows)
 __global__ __launch_bounds__(256) void k_distinctive(const uint32_t* desc, const int* offsets, int np, int* best) {
@@ -412,30 +383,10 @@ int orbfe_search_by_bow_kf2(const orbfe_keypoint* keys1, const uint8_t* desc1, c
     const int lim1 = nleft1 >= 0 ? nleft1 : n1, lim2 = nleft2 >= 0 ? nleft2 : n2;
     for (int i = 0; i < n1; i++) out12[i] = -1;
     if (n1 == 0 || n2 == 0 || fv1->n_nodes <= 0 || fv2->n_nodes <= 0) return 0;
-    for (const orbfe_feature_vector* fv : {fv1, fv2}) {
-        if (!fv->node_ids || !fv->offsets || fv->offsets[0] != 0) return ORBFE_E_ARG;
-        for (int i = 0; i < fv->n_nodes; i++)
-            if (fv->offsets[i + 1] < fv->offsets[i] || (i > 0 && fv->node_ids[i] <= fv->node_ids[i - 1]))
-                return ORBFE_E_ARG;
-    }
-    // each keypoint index belongs to one node of its FeatureVector (per-node threads rely on it)
-    auto unique_in_range = [](const orbfe_feature_vector* fv, int n) {
-        std::vector<uint8_t> seen(n, 0);
-        for (int i = 0; i < fv->offsets[fv->n_nodes]; i++) {
-            const uint32_t x = fv->indices[i];
-            if (x >= (uint32_t)n || seen[x]) return false;
-            seen[x] = 1;
-        }
-        return true;
-    };
-    if (!unique_in_range(fv1, n1) || !unique_in_range(fv2, n2)) return ORBFE_E_ARG;
+    if (!fv_shape_ok(fv1) || !fv_shape_ok(fv2)) return ORBFE_E_ARG;
+    if (!fv_indices_unique(fv1, n1) || !fv_indices_unique(fv2, n2)) return ORBFE_E_ARG;
     std::vector<int32_t> pairs;
-    int a = 0, b = 0;
-    while (a < fv1->n_nodes && b < fv2->n_nodes) {
-        if (fv1->node_ids[a] == fv2->node_ids[b]) { pairs.push_back(a); pairs.push_back(b); a++; b++; }
-        else if (fv1->node_ids[a] < fv2->node_ids[b]) a++;
-        else b++;
-    }
+    fv_join(fv1->node_ids, fv1->n_nodes, fv2->node_ids, fv2->n_nodes, pairs);
     if (pairs.empty()) return 0;
     const int npairs = (int)pairs.size() / 2;
     const int m1 = fv1->offsets[fv1->n_nodes], m2 = fv2->offsets[fv2->n_nodes];
@@ -463,9 +414,10 @@ int orbfe_search_by_bow_kf2(const orbfe_keypoint* keys1, const uint8_t* desc1, c
                        ms_ptr<const uint32_t>(o_idx2), ms_ptr<const int32_t>(o_mp1), ms_ptr<const int32_t>(o_mp2),
                        ms_ptr<const uint32_t>(o_d1), ms_ptr<const uint32_t>(o_d2), nnratio, ms_ptr<int>(o_m2),
                        ms_ptr<int>(o_oi), lim1, lim2);
-    hipLaunchKernelGGL(k_bow_kfkf_commit, dim3(1), dim3(1024), 0, s, ms_ptr<const OrbKeyPoint>(o_k1),
-                       ms_ptr<const OrbKeyPoint>(o_k2), n1, ms_ptr<const int32_t>(o_mp2), checkOri,
-                       ms_ptr<const int>(o_oi), ms_ptr<int>(o_out), ms_ptr<int>(o_res));
+    hipLaunchKernelGGL((k_bow_commit<true, AngKeys, AngKeys>), dim3(1), dim3(1024), 0, s,
+                       AngKeys{ms_ptr<const OrbKeyPoint>(o_k1)}, AngKeys{ms_ptr<const OrbKeyPoint>(o_k2)}, n1,
+                       ms_ptr<const int32_t>(o_mp2), checkOri, ms_ptr<const int>(o_oi), ms_ptr<int>(o_out),
+                       ms_ptr<int>(o_res));
     HIPCHK(hipGetLastError());
     timer.end();
     int nm = 0;
@@ -535,16 +487,7 @@ bool pose_ok(const orbfe_pose* p) { return p && (p->kind == ORBFE_SE3 || p->kind
 bool fv_ok(const orbfe_feature_vector* fv, int n) {
     if (!fv || fv->n_nodes < 0) return false;
     if (fv->n_nodes == 0) return true;
-    if (!fv->node_ids || !fv->offsets || !fv->indices || fv->offsets[0] != 0) return false;
-    for (int i = 0; i < fv->n_nodes; i++)
-        if (fv->offsets[i + 1] < fv->offsets[i] || (i > 0 && fv->node_ids[i] <= fv->node_ids[i - 1])) return false;
-    std::vector<uint8_t> seen(n > 0 ? n : 1, 0);
-    for (int i = 0; i < fv->offsets[fv->n_nodes]; i++) {
-        const uint32_t x = fv->indices[i];
-        if (x >= (uint32_t)n || seen[x]) return false;
-        seen[x] = 1;
-    }
-    return true;
+    return fv->indices && fv_shape_ok(fv) && fv_indices_unique(fv, n);
 }
 
 }  // namespace
@@ -614,9 +557,11 @@ int orbfe_search_for_triangulation(const orbfe_frame* KF1, const int32_t* mp1, c
                        u2 ? ms_ptr<const float>(o_u2) : nullptr, ms_ptr<const int32_t>(o_mp1),
                        ms_ptr<const int32_t>(o_mp2), ms_ptr<const float>(o_sc2), ms_ptr<const float>(o_sg2), ta,
                        ms_ptr<int>(o_oi));
-    hipLaunchKernelGGL(k_bow_kfkf_commit, dim3(1), dim3(1024), 0, s, ms_ptr<const OrbKeyPoint>(o_k1),
-                       ms_ptr<const OrbKeyPoint>(o_k2), n1, (const int32_t*)nullptr, checkOri, ms_ptr<const int>(o_oi),
-                       ms_ptr<int>(o_out), ms_ptr<int>(o_res));
+    // the row holds the matched KF2 index itself (no handles)
+    hipLaunchKernelGGL((k_bow_commit<true, AngKeys, AngKeys>), dim3(1), dim3(1024), 0, s,
+                       AngKeys{ms_ptr<const OrbKeyPoint>(o_k1)}, AngKeys{ms_ptr<const OrbKeyPoint>(o_k2)}, n1,
+                       (const int32_t*)nullptr, checkOri, ms_ptr<const int>(o_oi), ms_ptr<int>(o_out),
+                       ms_ptr<int>(o_res));
     HIPCHK(hipGetLastError());
     timer.end();
     int nm = 0;

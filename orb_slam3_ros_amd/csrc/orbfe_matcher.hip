@@ -467,6 +467,10 @@ __device__ __forceinline__ unsigned long long mt_min64_dpp_step(unsigned long lo
     const unsigned long long o = ((unsigned long long)oh << 32) | ol;
     return o < v ? o : v;
 }
+__device__ __forceinline__ unsigned long long quad_min64(unsigned long long v) {   // every lane: its quad's min
+    v = mt_min64_dpp_step<0xB1>(v);
+    return mt_min64_dpp_step<0x4E>(v);
+}
 __device__ __forceinline__ int mt_row_incl_scan(int v) {   // inclusive scan within each row of 16 lanes
     v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);   // row_shr:1
     v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);   // row_shr:2
@@ -3005,27 +3009,44 @@ __global__ __launch_bounds__(MT_NT) void k_bow_nodes(const int* pairs, int npair
         }
     }
 }
-__global__ __launch_bounds__(1024) void k_bow_commit(const OrbKeyPoint* kf_keys, const OrbKeyPoint* f_keys, int fn,
-                                                     const int32_t* kf_mp, int checkOri, const int* out_src,
-                                                     int* out, int* result) {
+// Where a commit reads a keypoint's angle: the keypoints themselves, or the angles alone (the pack of
+// a resident keyframe keeps only those)
+struct AngKeys {
+    const OrbKeyPoint* keys;
+    __device__ __forceinline__ float operator()(int i) const { return keys[i].angle; }
+};
+struct AngFlat {
+    const float* ang;
+    __device__ __forceinline__ float operator()(int i) const { return ang[i]; }
+};
+// The rotation-consistency commit of every multi-launch SearchByBoW form (ORBmatcher.cc:373-395 for
+// KF-F, :862-900 for KF-KF) and of SearchForTriangulation: match[i] is the index matched to own index i
+// (-1: none); a match whose rotation bin is not among the three maxima is dropped; the row holds the
+// matched side's handle mp[j], or j itself without handles. The reference bins rot = angle(KF) -
+// angle(F) in KF-F, where the row is F's (the matched side's angle first), and angle(KF1) - angle(KF2)
+// in KF-KF, where the row is KF1's (the own side's first): OWN_FIRST.
+template <bool OWN_FIRST, class OwnAng, class MatchedAng>
+__global__ __launch_bounds__(1024) void k_bow_commit(OwnAng own, MatchedAng matched, int n, const int32_t* mp,
+                                                     int checkOri, const int* match, int* out, int* result) {
     __shared__ int s_hist[MT_HISTO];
     __shared__ unsigned s_keep;
     __shared__ int s_n;
     if (threadIdx.x < MT_HISTO) s_hist[threadIdx.x] = 0;
     if (threadIdx.x == 0) s_n = 0;
     SYNC();
-    for (int i = threadIdx.x; i < fn; i += blockDim.x) {
-        const int s = out_src[i];
-        if (s >= 0 && checkOri) atomicAdd(&s_hist[mt_rot_bin(kf_keys[s].angle, f_keys[i].angle)], 1);
+    auto bin = [&](int i, int j) { return OWN_FIRST ? mt_rot_bin(own(i), matched(j)) : mt_rot_bin(matched(j), own(i)); };
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int j = match[i];
+        if (j >= 0 && checkOri) atomicAdd(&s_hist[bin(i, j)], 1);
     }
     SYNC();
     if (threadIdx.x == 0) s_keep = checkOri ? mt_three_maxima_keep(s_hist) : 0xFFFFFFFFu;
     SYNC();
     int cnt = 0;
-    for (int i = threadIdx.x; i < fn; i += blockDim.x) {
-        const int s = out_src[i];
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int j = match[i];
         int o = -1;
-        if (s >= 0 && (!checkOri || ((s_keep >> mt_rot_bin(kf_keys[s].angle, f_keys[i].angle)) & 1u))) o = kf_mp[s];
+        if (j >= 0 && (!checkOri || ((s_keep >> bin(i, j)) & 1u))) o = mp ? mp[j] : j;
         out[i] = o;
         cnt += o >= 0 ? 1 : 0;
     }
@@ -3034,13 +3055,208 @@ __global__ __launch_bounds__(1024) void k_bow_commit(const OrbKeyPoint* kf_keys,
     if (threadIdx.x == 0) result[0] = s_n;
 }
 
-// SearchByBoW(KF, F) in ONE workgroup (the Tracking thread's TrackReferenceKeyFrame / Relocalization
-// calls, Tracking.cc:2836,3765): both descriptor sets, the node lists and the match state in LDS, the
-// node walks of k_bow_nodes (same order, same two-camera rule) reading LDS only, and k_bow_commit's
-// rotation histogram in the same block. One launch; the multi-launch pair above serves the sets
-// that do not fit.
+// ---- The one-workgroup forms (k_bow_block, k_bow_batch, k_bow_kfkf_batch) share the node walk and the
+// in-block commit below. Each kernel keeps what is its own: staging, LDS layout, how it finds the node
+// pairs, and how it reports completion.
 #define MT_BOW_NT 1024
-#define MT_BOW_FR 4   // F features per thread in the commit (fn <= 4096)
+#define MT_BOW_FR 4   // row entries per thread in the commit (row length <= 4096)
+
+// The acceptance rules of the walk. A is the side walked feature by feature (the keyframe, KF1), B the
+// side searched for each of them (the frame, KF2). record(a, b) writes a match; matched(b) / mark(b)
+// are the "already matched" state of a node walked in LDS (a node walked in registers keeps a mask).
+// SearchByBoW(KF, F), ORBmatcher.cc:244-371: a KF feature without map point is skipped; an F feature
+// already matched is neither best nor second best; a two-camera F (nleft >= 0) keeps a separate best
+// among its right indices (:288-313); a match needs bestDist1 <= TH_LOW and float(bestDist1) <
+// nnratio * float(bestDist2), and the right best is taken inside the left's bestDist1 <= TH_LOW with
+// its ratio test disabled ("|| true", :359).
+struct BowRulesKfF {
+    static constexpr bool RIGHT = true;
+    const int* mp;   // KF handles
+    int* src;        // F index -> matched KF index (-1): the record and the "matched" state in one
+    int nleft;
+    float nnratio;
+    __device__ __forceinline__ bool skip_a(int a) const { return mp[a] < 0; }
+    __device__ __forceinline__ bool excluded(int) const { return false; }
+    __device__ __forceinline__ bool matched(int b) const { return src[b] >= 0; }
+    __device__ __forceinline__ bool is_left(int b) const { return nleft < 0 || b < nleft; }
+    __device__ __forceinline__ bool low(int d) const { return d <= MT_TH_LOW; }
+    __device__ __forceinline__ void record(int a, int b) const { src[b] = a; }
+    __device__ __forceinline__ void mark(int) const {}
+};
+// SearchByBoW(KF1, KF2), ORBmatcher.cc:790-860: a KF1 feature without map point or at an index >= lim1
+// is skipped; a KF2 feature without map point, at an index >= lim2 or already matched (vbMatched2) is
+// neither best nor second best; no right-camera best; a match needs bestDist1 < TH_LOW (strict) and
+// the same ratio test.
+struct BowRulesKfKf {
+    static constexpr bool RIGHT = false;
+    const int *mp1, *mp2;
+    int* m12;         // KF1 index -> matched KF2 index (-1)
+    uint8_t* taken;   // vbMatched2 of the nodes walked in LDS
+    int lim1, lim2;
+    float nnratio;
+    __device__ __forceinline__ bool skip_a(int a) const { return a >= lim1 || mp1[a] < 0; }
+    __device__ __forceinline__ bool excluded(int b) const { return b >= lim2 || mp2[b] < 0; }
+    __device__ __forceinline__ bool matched(int b) const { return taken[b]; }
+    __device__ __forceinline__ bool is_left(int) const { return true; }
+    __device__ __forceinline__ bool low(int d) const { return d < MT_TH_LOW; }
+    __device__ __forceinline__ void record(int a, int b) const { m12[a] = b; }
+    __device__ __forceinline__ void mark(int b) const { taken[b] = 1; }
+};
+
+__device__ __forceinline__ int bow_dist(uint4 k0, uint4 k1, uint4 f0, uint4 f1) {
+    return __popc(k0.x ^ f0.x) + __popc(k0.y ^ f0.y) + __popc(k0.z ^ f0.z) + __popc(k0.w ^ f0.w) +
+           __popc(k1.x ^ f1.x) + __popc(k1.y ^ f1.y) + __popc(k1.z ^ f1.z) + __popc(k1.w ^ f1.w);
+}
+// One node present in both vectors, walked by one quad of lanes (sl: the lane in the quad), everything
+// read from LDS: the node's A features [a0, a1) of s_ia run in the FeatureVector's stored order (the
+// reference's); for each, the quad's lanes score the node's B features [b0, b1) of s_ib (lane l:
+// positions l, l + 4, ...) and the quad minimum of (dist, position) keys is the reference's first best,
+// the second minimum its bestDist2. An index belongs to one node only, so the "already matched" state
+// of the node's B features is private to the quad. One thread per node walked the longest node's A x B
+// pairs alone (16-18 us of k_bow_block's 26); a row of 16 lanes per node spent more on its reductions
+// than it saved at ~2.5 features per node (28 us).
+template <class Rules>
+__device__ __forceinline__ void bow_walk_node(int a0, int a1, int b0, int b1, const int* s_ia, const int* s_ib,
+                                              const uint4* s_da, const uint4* s_db, int sl, const Rules R) {
+    constexpr int FQ = 4;   // B features per lane held in registers (nodes of <= 16 B features)
+    if (b1 - b0 <= 4 * FQ) {
+        // the node's B features in registers (position p = 4 q + lane: the reference's order); the bit
+        // mask holds the excluded and the matched ones alike: no LDS round trip inside the A walk
+        uint4 fd0[FQ], fd1[FQ];
+        int idx[FQ];
+        unsigned taken = 0u, isleft = 0u;
+#pragma unroll
+        for (int q = 0; q < FQ; q++) {
+            const int ib = b0 + sl + 4 * q;
+            idx[q] = ib < b1 ? s_ib[ib] : 0;
+            if (ib < b1 && !R.excluded(idx[q])) {
+                fd0[q] = s_db[2 * idx[q]];
+                fd1[q] = s_db[2 * idx[q] + 1];
+                if (Rules::RIGHT && R.is_left(idx[q])) isleft |= 1u << q;
+            } else {
+                fd0[q] = fd1[q] = make_uint4(0u, 0u, 0u, 0u);
+                taken |= 1u << q;
+            }
+        }
+        for (int ia = a0; ia < a1; ia++) {
+            const int a = s_ia[ia];
+            if (R.skip_a(a)) continue;
+            const uint4 k0 = s_da[2 * a], k1 = s_da[2 * a + 1];
+            unsigned long long m_b1 = ~0ull, m_b2 = ~0ull, m_r1 = ~0ull;
+#pragma unroll
+            for (int q = 0; q < FQ; q++) {
+                if ((taken >> q) & 1u) continue;
+                const int dist = bow_dist(k0, k1, fd0[q], fd1[q]);
+                const unsigned long long key = ((unsigned long long)dist << 32) | (unsigned)(4 * q + sl);
+                if (!Rules::RIGHT || ((isleft >> q) & 1u)) {
+                    if (key < m_b1) { m_b2 = m_b1; m_b1 = key; }
+                    else if (key < m_b2) m_b2 = key;
+                } else if (key < m_r1) {
+                    m_r1 = key;
+                }
+            }
+            const unsigned long long m1 = quad_min64(m_b1);
+            const unsigned long long m2 = quad_min64(m_b1 == m1 ? m_b2 : m_b1);
+            unsigned long long mr = ~0ull;
+            if constexpr (Rules::RIGHT) mr = quad_min64(m_r1);
+            const int bestDist1 = m1 != ~0ull ? (int)(m1 >> 32) : 256;
+            const int bestDist2 = m2 != ~0ull ? (int)(m2 >> 32) : 256;
+            const int bestDist1R = mr != ~0ull ? (int)(mr >> 32) : 256;
+            int w1 = -1, wr = -1;   // winning positions
+            if (R.low(bestDist1)) {
+                if (static_cast<float>(bestDist1) < R.nnratio * static_cast<float>(bestDist2)) w1 = (int)(m1 & 0xFFFFFFFFu);
+                if (Rules::RIGHT && R.low(bestDist1R)) wr = (int)(mr & 0xFFFFFFFFu);
+            }
+#pragma unroll
+            for (int q = 0; q < FQ; q++) {
+                if (w1 == 4 * q + sl || wr == 4 * q + sl) {
+                    taken |= 1u << q;
+                    R.record(a, idx[q]);
+                }
+            }
+        }
+        return;
+    }
+    // larger nodes: the B features and their flags read from LDS per A feature
+    for (int ia = a0; ia < a1; ia++) {
+        const int a = s_ia[ia];
+        if (R.skip_a(a)) continue;
+        const uint4 k0 = s_da[2 * a], k1 = s_da[2 * a + 1];
+        unsigned long long m_b1 = ~0ull, m_b2 = ~0ull, m_r1 = ~0ull;
+        for (int ib = b0 + sl; ib < b1; ib += 4) {
+            const int b = s_ib[ib];
+            if (R.excluded(b) || R.matched(b)) continue;
+            const int dist = bow_dist(k0, k1, s_db[2 * b], s_db[2 * b + 1]);
+            const unsigned long long key = ((unsigned long long)dist << 32) | (unsigned)ib;
+            if (!Rules::RIGHT || R.is_left(b)) {
+                if (key < m_b1) { m_b2 = m_b1; m_b1 = key; }
+                else if (key < m_b2) m_b2 = key;
+            } else if (key < m_r1) {
+                m_r1 = key;
+            }
+        }
+        const unsigned long long m1 = quad_min64(m_b1);
+        const unsigned long long m2 = quad_min64(m_b1 == m1 ? m_b2 : m_b1);
+        unsigned long long mr = ~0ull;
+        if constexpr (Rules::RIGHT) mr = quad_min64(m_r1);
+        if (sl == 0) {
+            const int bestDist1 = m1 != ~0ull ? (int)(m1 >> 32) : 256;
+            const int bestDist2 = m2 != ~0ull ? (int)(m2 >> 32) : 256;
+            const int bestDist1R = mr != ~0ull ? (int)(mr >> 32) : 256;
+            auto take = [&](unsigned long long m) {   // the winner at position (m & 0xFFFFFFFF)
+                const int b = s_ib[(int)(m & 0xFFFFFFFFu)];
+                R.record(a, b);
+                R.mark(b);
+            };
+            if (R.low(bestDist1)) {
+                if (static_cast<float>(bestDist1) < R.nnratio * static_cast<float>(bestDist2)) take(m1);
+                if (Rules::RIGHT && R.low(bestDist1R)) take(mr);
+            }
+        }
+        WAVE_SYNC();   // the quad's next A feature sees the matched B features
+    }
+}
+
+// The tail of the same three kernels: rotation consistency and the output row. match[i] is the index
+// matched to own index i < n (-1: none), own(u, i) the angle of own index i = tid + u * MT_BOW_NT,
+// matched(j) that of matched index j, mp the matched side's handles; OWN_FIRST as in k_bow_commit.
+// The caller's s_hist is zeroed, s_n is 0 and a barrier has passed since the last write to match;
+// on return s_n is being counted: a barrier before it is read.
+template <bool OWN_FIRST, class OwnAng, class MatchedAng>
+__device__ __forceinline__ void bow_commit_rows(int n, const int* match, OwnAng own, MatchedAng matched, const int* mp,
+                                                int checkOri, int* out, int* s_hist, unsigned* s_keep, int* s_n) {
+    const int tid = threadIdx.x;
+    int sidx[MT_BOW_FR], bin[MT_BOW_FR];
+#pragma unroll
+    for (int u = 0; u < MT_BOW_FR; u++) {
+        const int i = tid + u * MT_BOW_NT;
+        sidx[u] = i < n ? match[i] : -1;
+        bin[u] = 0;
+        if (sidx[u] >= 0)
+            bin[u] = OWN_FIRST ? mt_rot_bin(own(u, i), matched(sidx[u])) : mt_rot_bin(matched(sidx[u]), own(u, i));
+        if (sidx[u] >= 0 && checkOri) atomicAdd(&s_hist[bin[u]], 1);
+    }
+    SYNC();
+    if (tid == 0) *s_keep = checkOri ? mt_three_maxima_keep(s_hist) : 0xFFFFFFFFu;
+    SYNC();
+    int cnt = 0;
+#pragma unroll
+    for (int u = 0; u < MT_BOW_FR; u++) {
+        const int i = tid + u * MT_BOW_NT;
+        if (i >= n) continue;
+        int o = -1;
+        if (sidx[u] >= 0 && (!checkOri || ((*s_keep >> bin[u]) & 1u))) o = mp[sidx[u]];
+        out[i] = o;
+        cnt += o >= 0 ? 1 : 0;
+    }
+    atomicAdd(s_n, cnt);
+}
+
+// SearchByBoW(KF, F) in ONE workgroup (the Tracking thread's TrackReferenceKeyFrame / Relocalization
+// calls, Tracking.cc:2836,3765): both descriptor sets, the node lists and the match state in LDS, one
+// quad per entry of the host's node-pair list (bow_walk_node under BowRulesKfF), the commit in the same
+// block, completion through the host's status words. One launch; k_bow_nodes + k_bow_commit serve the
+// sets that do not fit.
 // The call's uploads are one contiguous device range (Plan), node pairs first and the F descriptors
 // last: the block copies that range into LDS with one flat 16-byte loop (independent loads in flight
 // together; a copy loop per array waited one memory latency per array) and addresses every array
@@ -3095,144 +3311,16 @@ __global__ __launch_bounds__(MT_BOW_NT) void k_bow_block(BowBlockIn in, int* out
     const uint4* s_kd = (const uint4*)(bw_sm + in.o_kfdesc);
     const OrbKeyPoint* s_kk = (const OrbKeyPoint*)(bw_sm + in.o_kfkeys);
     const uint4* s_fd = (const uint4*)(bw_sm + in.o_fdesc);
-    // one quad of lanes per node present in both vectors (ORBmatcher.cc:244-371). The node's KF
-    // features run in the reference's order; for each, the quad's lanes score the node's F features
-    // (lane l: l, l + 4, ...) and the quad minimum of (dist, position) keys is the reference's first
-    // best, the second minimum its bestDist2. An F index belongs to one node only, so the "already
-    // matched" state is private to the quad. One thread per node walked the longest node's KF x F
-    // pairs alone (16-18 us of the kernel's 26); a row of 16 lanes per node spent more on its
-    // reductions than it saved at ~2.5 features per node (28 us).
-    const int sl = tid & 3;
-    auto quad_min64 = [](unsigned long long v) {
-        v = mt_min64_dpp_step<0xB1>(v);
-        return mt_min64_dpp_step<0x4E>(v);
-    };
-    constexpr int FQ = 4;   // F features per lane held in registers (nodes of <= 16 F features)
+    const BowRulesKfF rules{s_mp, s_src, in.nleft, in.nnratio};
     for (int t = tid >> 2; t < in.npairs; t += MT_BOW_NT / 4) {
         const int a = s_pr[2 * t], b = s_pr[2 * t + 1];
-        const int fb0 = s_fo[b], fb1 = s_fo[b + 1];
-        const int ka0 = s_kfo[a], ka1 = s_kfo[a + 1];
-        if (fb1 - fb0 <= 4 * FQ) {
-            // the node's F features in registers (position p = 4 c + lane: the reference's order), the
-            // "already matched" flags as a bit mask: no LDS round trip inside the KF walk
-            uint4 fd0[FQ], fd1[FQ];
-            int fidx[FQ];
-            unsigned taken = 0u, isleft = 0u;
-#pragma unroll
-            for (int c = 0; c < FQ; c++) {
-                const int ib = fb0 + sl + 4 * c;
-                fidx[c] = ib < fb1 ? s_fi[ib] : 0;
-                if (ib < fb1) {
-                    fd0[c] = s_fd[2 * fidx[c]];
-                    fd1[c] = s_fd[2 * fidx[c] + 1];
-                    if (in.nleft < 0 || fidx[c] < in.nleft) isleft |= 1u << c;
-                } else {
-                    fd0[c] = fd1[c] = make_uint4(0u, 0u, 0u, 0u);
-                    taken |= 1u << c;
-                }
-            }
-            for (int ia = ka0; ia < ka1; ia++) {
-                const int realIdxKF = s_kfi[ia];
-                if (s_mp[realIdxKF] < 0) continue;
-                const uint4 k0 = s_kd[2 * realIdxKF], k1 = s_kd[2 * realIdxKF + 1];
-                unsigned long long b1 = ~0ull, b2 = ~0ull, r1 = ~0ull;
-#pragma unroll
-                for (int c = 0; c < FQ; c++) {
-                    if ((taken >> c) & 1u) continue;
-                    const int dist = __popc(k0.x ^ fd0[c].x) + __popc(k0.y ^ fd0[c].y) + __popc(k0.z ^ fd0[c].z) +
-                                     __popc(k0.w ^ fd0[c].w) + __popc(k1.x ^ fd1[c].x) + __popc(k1.y ^ fd1[c].y) +
-                                     __popc(k1.z ^ fd1[c].z) + __popc(k1.w ^ fd1[c].w);
-                    const unsigned long long key = ((unsigned long long)dist << 32) | (unsigned)(4 * c + sl);
-                    if ((isleft >> c) & 1u) {
-                        if (key < b1) { b2 = b1; b1 = key; }
-                        else if (key < b2) b2 = key;
-                    } else if (key < r1) {
-                        r1 = key;
-                    }
-                }
-                const unsigned long long m1 = quad_min64(b1);
-                const unsigned long long m2 = quad_min64(b1 == m1 ? b2 : b1);
-                const unsigned long long mr = quad_min64(r1);
-                const int bestDist1 = m1 != ~0ull ? (int)(m1 >> 32) : 256;
-                const int bestDist2 = m2 != ~0ull ? (int)(m2 >> 32) : 256;
-                const int bestDist1R = mr != ~0ull ? (int)(mr >> 32) : 256;
-                int w1 = -1, wr = -1;   // winning positions
-                if (bestDist1 <= MT_TH_LOW) {
-                    if (static_cast<float>(bestDist1) < in.nnratio * static_cast<float>(bestDist2)) w1 = (int)(m1 & 0xFFFFFFFFu);
-                    if (bestDist1R <= MT_TH_LOW) wr = (int)(mr & 0xFFFFFFFFu);
-                }
-#pragma unroll
-                for (int c = 0; c < FQ; c++) {
-                    if (w1 == 4 * c + sl || wr == 4 * c + sl) {
-                        taken |= 1u << c;
-                        s_src[fidx[c]] = realIdxKF;
-                    }
-                }
-            }
-            continue;
-        }
-        // larger nodes: the F features and their flags read from LDS per KF feature
-        for (int ia = ka0; ia < ka1; ia++) {
-            const int realIdxKF = s_kfi[ia];
-            if (s_mp[realIdxKF] < 0) continue;
-            const uint4 k0 = s_kd[2 * realIdxKF], k1 = s_kd[2 * realIdxKF + 1];
-            unsigned long long b1 = ~0ull, b2 = ~0ull, r1 = ~0ull;
-            for (int ib = fb0 + sl; ib < fb1; ib += 4) {
-                const int realIdxF = s_fi[ib];
-                if (s_src[realIdxF] >= 0) continue;
-                const uint4 f0 = s_fd[2 * realIdxF], f1 = s_fd[2 * realIdxF + 1];
-                const int dist = __popc(k0.x ^ f0.x) + __popc(k0.y ^ f0.y) + __popc(k0.z ^ f0.z) + __popc(k0.w ^ f0.w) +
-                                 __popc(k1.x ^ f1.x) + __popc(k1.y ^ f1.y) + __popc(k1.z ^ f1.z) + __popc(k1.w ^ f1.w);
-                const unsigned long long key = ((unsigned long long)dist << 32) | (unsigned)ib;
-                if (in.nleft < 0 || realIdxF < in.nleft) {
-                    if (key < b1) { b2 = b1; b1 = key; }
-                    else if (key < b2) b2 = key;
-                } else if (key < r1) {
-                    r1 = key;
-                }
-            }
-            const unsigned long long m1 = quad_min64(b1);
-            const unsigned long long m2 = quad_min64(b1 == m1 ? b2 : b1);
-            const unsigned long long mr = quad_min64(r1);
-            if (sl == 0) {
-                const int bestDist1 = m1 != ~0ull ? (int)(m1 >> 32) : 256;
-                const int bestDist2 = m2 != ~0ull ? (int)(m2 >> 32) : 256;
-                const int bestDist1R = mr != ~0ull ? (int)(mr >> 32) : 256;
-                if (bestDist1 <= MT_TH_LOW) {
-                    if (static_cast<float>(bestDist1) < in.nnratio * static_cast<float>(bestDist2))
-                        s_src[s_fi[(int)(m1 & 0xFFFFFFFFu)]] = realIdxKF;
-                    if (bestDist1R <= MT_TH_LOW) s_src[s_fi[(int)(mr & 0xFFFFFFFFu)]] = realIdxKF;
-                }
-            }
-            WAVE_SYNC();   // the quad's next KF feature sees the taken F features
-        }
+        bow_walk_node(s_kfo[a], s_kfo[a + 1], s_fo[b], s_fo[b + 1], s_kfi, s_fi, s_kd, s_fd, tid & 3, rules);
     }
     SYNC();
     BOW_STAMP(2);
-    // rotation consistency (ORBmatcher.cc:373-395) and the output (k_bow_commit); F's angles were
-    // loaded at the start
-    int sidx[MT_BOW_FR], bin[MT_BOW_FR];
-#pragma unroll
-    for (int u = 0; u < MT_BOW_FR; u++) {
-        const int i = tid + u * MT_BOW_NT;
-        sidx[u] = i < in.fn ? s_src[i] : -1;
-        bin[u] = sidx[u] >= 0 ? mt_rot_bin(s_kk[sidx[u]].angle, fang[u]) : 0;
-        if (sidx[u] >= 0 && in.checkOri) atomicAdd(&s_hist[bin[u]], 1);
-    }
-    SYNC();
-    if (tid == 0) s_keep = in.checkOri ? mt_three_maxima_keep(s_hist) : 0xFFFFFFFFu;
-    SYNC();
-    int cnt = 0;
-#pragma unroll
-    for (int u = 0; u < MT_BOW_FR; u++) {
-        const int i = tid + u * MT_BOW_NT;
-        if (i >= in.fn) continue;
-        int o = -1;
-        if (sidx[u] >= 0 && (!in.checkOri || ((s_keep >> bin[u]) & 1u))) o = s_mp[sidx[u]];
-        out[i] = o;
-        cnt += o >= 0 ? 1 : 0;
-    }
-    atomicAdd(&s_n, cnt);
+    // F's angles were loaded at the start
+    bow_commit_rows<false>(in.fn, s_src, [&](int u, int) { return fang[u]; }, AngKeys{s_kk}, s_mp, in.checkOri, out,
+                           s_hist, &s_keep, &s_n);
     // every wave's output stores complete (vmcnt 0), the barrier, then one system-scope release before
     // the status words the host waits for (as k_sbp_block)
     __builtin_amdgcn_s_waitcnt(0);
@@ -3256,12 +3344,13 @@ __global__ __launch_bounds__(MT_BOW_NT) void k_bow_block(BowBlockIn in, int* out
 }
 
 // SearchByBoW(kfs[c], F) for every candidate of Tracking::Relocalization's first loop in ONE launch
-// (Tracking.cc:3680-3701): workgroup c is k_bow_block on candidate c. The keyframe side is the
+// (Tracking.cc:3680-3701), one workgroup per candidate c. The keyframe side is the
 // resident pack of an orbfe_keyframe (node ids, CSR, angles, descriptors: what the search reads, laid
 // out at create so that staging is one flat 16-byte copy); the frame side (node ids, CSR, descriptors,
 // keypoints) is in HBM once for all workgroups; only kf_mp[c] crosses the link per candidate. A KF
-// node finds its F node by binary search of F's node ids in LDS (the reference's lower_bound walk,
-// ORBmatcher.cc:244-371, gives the same pairs), so no pair list exists.
+// node finds its F node by binary search of F's node ids in LDS (the reference's lower_bound walk
+// gives the same pairs), so no pair list exists; the node is walked by bow_walk_node under BowRulesKfF
+// and the row committed in the block; nm[c] is written last and read after a stream synchronisation.
 struct BowCand {
     const uint4* pack;   // the resident pack: node ids at byte 0, then the arrays at the offsets below
     int nvec;            // 16-byte words of the pack
@@ -3269,7 +3358,7 @@ struct BowCand {
     int nn, kf_n;        // nodes, features
     int mp_vec;          // kf_mp[c]: 16-byte word index from BowBatchIn::mp_base
     int mode;            // 0: match here; 1: NULL / empty candidate, the row is -1; 2: the multi-launch
-                         //    path (k_bow_nodes + k_bow_commit_ang) writes this row
+                         //    path (k_bow_nodes + k_bow_commit) writes this row
 };
 struct BowBatchIn {
     const BowCand* cands;
@@ -3337,16 +3426,8 @@ __global__ __launch_bounds__(MT_BOW_NT) void k_bow_batch(BowBatchIn in) {
     const uint4* s_kd = (const uint4*)((const uint8_t*)s_kf + cd.o_desc);
     const uint4* s_fd = s_fdw;
     const int* s_mp = (const int*)s_mpw;
-    // the node walks are k_bow_block's, restated (that kernel stays as it is): one quad of lanes per KF
-    // node, the node's KF features in the reference's order, the quad minimum of (dist, position) keys
-    // the reference's first best
-    const int sl = tid & 3;
-    auto quad_min64 = [](unsigned long long v) {
-        v = mt_min64_dpp_step<0xB1>(v);
-        return mt_min64_dpp_step<0x4E>(v);
-    };
-    constexpr int FQ = 4;   // F features per lane held in registers (nodes of <= 16 F features)
-    for (int a = tid >> 2; a < cd.nn; a += MT_BOW_NT / 4) {
+    const BowRulesKfF rules{s_mp, s_src, in.nleft, in.nnratio};
+    for (int a = tid >> 2; a < cd.nn; a += MT_BOW_NT / 4) {   // one quad per KF node
         const unsigned id = s_knid[a];
         int b = 0, hi = in.fnn;   // lower_bound of the node id among F's (the quad's lanes agree)
         while (b < hi) {
@@ -3355,157 +3436,13 @@ __global__ __launch_bounds__(MT_BOW_NT) void k_bow_batch(BowBatchIn in) {
             else hi = mid;
         }
         if (b >= in.fnn || s_fnid[b] != id) continue;
-        const int fb0 = s_fo[b], fb1 = s_fo[b + 1];
-        const int ka0 = s_kfo[a], ka1 = s_kfo[a + 1];
-        if (fb1 - fb0 <= 4 * FQ) {
-            uint4 fd0[FQ], fd1[FQ];
-            int fidx[FQ];
-            unsigned taken = 0u, isleft = 0u;
-#pragma unroll
-            for (int q = 0; q < FQ; q++) {
-                const int ib = fb0 + sl + 4 * q;
-                fidx[q] = ib < fb1 ? s_fi[ib] : 0;
-                if (ib < fb1) {
-                    fd0[q] = s_fd[2 * fidx[q]];
-                    fd1[q] = s_fd[2 * fidx[q] + 1];
-                    if (in.nleft < 0 || fidx[q] < in.nleft) isleft |= 1u << q;
-                } else {
-                    fd0[q] = fd1[q] = make_uint4(0u, 0u, 0u, 0u);
-                    taken |= 1u << q;
-                }
-            }
-            for (int ia = ka0; ia < ka1; ia++) {
-                const int realIdxKF = s_kfi[ia];
-                if (s_mp[realIdxKF] < 0) continue;
-                const uint4 k0 = s_kd[2 * realIdxKF], k1 = s_kd[2 * realIdxKF + 1];
-                unsigned long long b1 = ~0ull, b2 = ~0ull, r1 = ~0ull;
-#pragma unroll
-                for (int q = 0; q < FQ; q++) {
-                    if ((taken >> q) & 1u) continue;
-                    const int dist = __popc(k0.x ^ fd0[q].x) + __popc(k0.y ^ fd0[q].y) + __popc(k0.z ^ fd0[q].z) +
-                                     __popc(k0.w ^ fd0[q].w) + __popc(k1.x ^ fd1[q].x) + __popc(k1.y ^ fd1[q].y) +
-                                     __popc(k1.z ^ fd1[q].z) + __popc(k1.w ^ fd1[q].w);
-                    const unsigned long long key = ((unsigned long long)dist << 32) | (unsigned)(4 * q + sl);
-                    if ((isleft >> q) & 1u) {
-                        if (key < b1) { b2 = b1; b1 = key; }
-                        else if (key < b2) b2 = key;
-                    } else if (key < r1) {
-                        r1 = key;
-                    }
-                }
-                const unsigned long long m1 = quad_min64(b1);
-                const unsigned long long m2 = quad_min64(b1 == m1 ? b2 : b1);
-                const unsigned long long mr = quad_min64(r1);
-                const int bestDist1 = m1 != ~0ull ? (int)(m1 >> 32) : 256;
-                const int bestDist2 = m2 != ~0ull ? (int)(m2 >> 32) : 256;
-                const int bestDist1R = mr != ~0ull ? (int)(mr >> 32) : 256;
-                int w1 = -1, wr = -1;   // winning positions
-                if (bestDist1 <= MT_TH_LOW) {
-                    if (static_cast<float>(bestDist1) < in.nnratio * static_cast<float>(bestDist2)) w1 = (int)(m1 & 0xFFFFFFFFu);
-                    if (bestDist1R <= MT_TH_LOW) wr = (int)(mr & 0xFFFFFFFFu);
-                }
-#pragma unroll
-                for (int q = 0; q < FQ; q++) {
-                    if (w1 == 4 * q + sl || wr == 4 * q + sl) {
-                        taken |= 1u << q;
-                        s_src[fidx[q]] = realIdxKF;
-                    }
-                }
-            }
-            continue;
-        }
-        // larger nodes: the F features and their flags read from LDS per KF feature
-        for (int ia = ka0; ia < ka1; ia++) {
-            const int realIdxKF = s_kfi[ia];
-            if (s_mp[realIdxKF] < 0) continue;
-            const uint4 k0 = s_kd[2 * realIdxKF], k1 = s_kd[2 * realIdxKF + 1];
-            unsigned long long b1 = ~0ull, b2 = ~0ull, r1 = ~0ull;
-            for (int ib = fb0 + sl; ib < fb1; ib += 4) {
-                const int realIdxF = s_fi[ib];
-                if (s_src[realIdxF] >= 0) continue;
-                const uint4 f0 = s_fd[2 * realIdxF], f1 = s_fd[2 * realIdxF + 1];
-                const int dist = __popc(k0.x ^ f0.x) + __popc(k0.y ^ f0.y) + __popc(k0.z ^ f0.z) + __popc(k0.w ^ f0.w) +
-                                 __popc(k1.x ^ f1.x) + __popc(k1.y ^ f1.y) + __popc(k1.z ^ f1.z) + __popc(k1.w ^ f1.w);
-                const unsigned long long key = ((unsigned long long)dist << 32) | (unsigned)ib;
-                if (in.nleft < 0 || realIdxF < in.nleft) {
-                    if (key < b1) { b2 = b1; b1 = key; }
-                    else if (key < b2) b2 = key;
-                } else if (key < r1) {
-                    r1 = key;
-                }
-            }
-            const unsigned long long m1 = quad_min64(b1);
-            const unsigned long long m2 = quad_min64(b1 == m1 ? b2 : b1);
-            const unsigned long long mr = quad_min64(r1);
-            if (sl == 0) {
-                const int bestDist1 = m1 != ~0ull ? (int)(m1 >> 32) : 256;
-                const int bestDist2 = m2 != ~0ull ? (int)(m2 >> 32) : 256;
-                const int bestDist1R = mr != ~0ull ? (int)(mr >> 32) : 256;
-                if (bestDist1 <= MT_TH_LOW) {
-                    if (static_cast<float>(bestDist1) < in.nnratio * static_cast<float>(bestDist2))
-                        s_src[s_fi[(int)(m1 & 0xFFFFFFFFu)]] = realIdxKF;
-                    if (bestDist1R <= MT_TH_LOW) s_src[s_fi[(int)(mr & 0xFFFFFFFFu)]] = realIdxKF;
-                }
-            }
-            WAVE_SYNC();   // the quad's next KF feature sees the taken F features
-        }
+        bow_walk_node(s_kfo[a], s_kfo[a + 1], s_fo[b], s_fo[b + 1], s_kfi, s_fi, s_kd, s_fd, tid & 3, rules);
     }
     SYNC();
-    // rotation consistency (ORBmatcher.cc:373-395) and the output row
-    int sidx[MT_BOW_FR], bin[MT_BOW_FR];
-#pragma unroll
-    for (int u = 0; u < MT_BOW_FR; u++) {
-        const int i = tid + u * MT_BOW_NT;
-        sidx[u] = i < in.fn ? s_src[i] : -1;
-        bin[u] = sidx[u] >= 0 ? mt_rot_bin(s_ang[sidx[u]], fang[u]) : 0;
-        if (sidx[u] >= 0 && in.checkOri) atomicAdd(&s_hist[bin[u]], 1);
-    }
-    SYNC();
-    if (tid == 0) s_keep = in.checkOri ? mt_three_maxima_keep(s_hist) : 0xFFFFFFFFu;
-    SYNC();
-    int cnt = 0;
-#pragma unroll
-    for (int u = 0; u < MT_BOW_FR; u++) {
-        const int i = tid + u * MT_BOW_NT;
-        if (i >= in.fn) continue;
-        int o = -1;
-        if (sidx[u] >= 0 && (!in.checkOri || ((s_keep >> bin[u]) & 1u))) o = s_mp[sidx[u]];
-        out[i] = o;
-        cnt += o >= 0 ? 1 : 0;
-    }
-    atomicAdd(&s_n, cnt);
+    bow_commit_rows<false>(in.fn, s_src, [&](int u, int) { return fang[u]; }, AngFlat{s_ang}, s_mp, in.checkOri, out,
+                           s_hist, &s_keep, &s_n);
     SYNC();
     if (tid == 0) in.nm[c] = s_n;   // the host reads the rows after a stream synchronisation
-}
-// k_bow_commit for a resident keyframe (the pack keeps the angles only): the multi-launch path of a
-// batch candidate that does not fit one workgroup's LDS
-__global__ __launch_bounds__(1024) void k_bow_commit_ang(const float* kf_ang, const OrbKeyPoint* f_keys, int fn,
-                                                         const int32_t* kf_mp, int checkOri, const int* out_src,
-                                                         int* out, int* result) {
-    __shared__ int s_hist[MT_HISTO];
-    __shared__ unsigned s_keep;
-    __shared__ int s_n;
-    if (threadIdx.x < MT_HISTO) s_hist[threadIdx.x] = 0;
-    if (threadIdx.x == 0) s_n = 0;
-    SYNC();
-    for (int i = threadIdx.x; i < fn; i += blockDim.x) {
-        const int s = out_src[i];
-        if (s >= 0 && checkOri) atomicAdd(&s_hist[mt_rot_bin(kf_ang[s], f_keys[i].angle)], 1);
-    }
-    SYNC();
-    if (threadIdx.x == 0) s_keep = checkOri ? mt_three_maxima_keep(s_hist) : 0xFFFFFFFFu;
-    SYNC();
-    int cnt = 0;
-    for (int i = threadIdx.x; i < fn; i += blockDim.x) {
-        const int s = out_src[i];
-        int o = -1;
-        if (s >= 0 && (!checkOri || ((s_keep >> mt_rot_bin(kf_ang[s], f_keys[i].angle)) & 1u))) o = kf_mp[s];
-        out[i] = o;
-        cnt += o >= 0 ? 1 : 0;
-    }
-    atomicAdd(&s_n, cnt);
-    SYNC();
-    if (threadIdx.x == 0) result[0] = s_n;
 }
 // the angles of a device-resident keyframe's keypoints, gathered into its pack at create
 __global__ void k_kf_angles(const OrbKeyPoint* keys, int n, float* ang) {
@@ -4657,6 +4594,43 @@ int sbp_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs
     return cnt[0] - cnt[1];
 }
 
+// ---- the FeatureVector checks and the node join of every SearchByBoW / SearchForTriangulation driver
+// A FeatureVector of n_nodes > 0: CSR offsets from 0 that never decrease, node ids strictly ascending.
+bool fv_shape_ok(const orbfe_feature_vector* fv) {
+    if (!fv->node_ids || !fv->offsets || fv->offsets[0] != 0) return false;
+    for (int i = 0; i < fv->n_nodes; i++)
+        if (fv->offsets[i + 1] < fv->offsets[i] || (i > 0 && fv->node_ids[i] <= fv->node_ids[i - 1])) return false;
+    return true;
+}
+// Every listed index (of a FeatureVector that passed fv_shape_ok) is < n and belongs to one node only
+// (DBoW2's transform; the per-node threads and quads rely on it). With `repeated` an index listed
+// twice is reported there instead of refused.
+bool fv_indices_unique(const orbfe_feature_vector* fv, int n, bool* repeated = nullptr) {
+    const int listed = fv->offsets[fv->n_nodes];
+    if (listed > 0 && !fv->indices) return false;
+    std::vector<uint8_t> seen(n > 0 ? n : 0, 0);
+    for (int i = 0; i < listed; i++) {
+        const uint32_t x = fv->indices[i];
+        if (x >= (uint32_t)n) return false;
+        if (seen[x]) {
+            if (!repeated) return false;
+            *repeated = true;
+        }
+        seen[x] = 1;
+    }
+    return true;
+}
+// Ordered merge-join of two ascending node-id lists (the reference's lower_bound walk,
+// ORBmatcher.cc:244-371): pairs = (position in a, position in b) of every shared id.
+void fv_join(const uint32_t* ids_a, int na, const uint32_t* ids_b, int nb, std::vector<int32_t>& pairs) {
+    int a = 0, b = 0;
+    while (a < na && b < nb) {
+        if (ids_a[a] == ids_b[b]) { pairs.push_back(a++); pairs.push_back(b++); }
+        else if (ids_a[a] < ids_b[b]) a++;
+        else b++;
+    }
+}
+
 }  // namespace
 
 // A keyframe's matcher-visible immutable features in HBM (orbfe_keyframe_create): one allocation,
@@ -4965,30 +4939,14 @@ int orbfe_search_by_bow(const orbfe_keypoint* kf_keys, const uint8_t* kf_desc, c
     const int fn = F->n;
     for (int i = 0; i < fn; i++) out[i] = -1;
     if (fn == 0 || kf_n == 0 || kf_fv->n_nodes <= 0 || f_fv->n_nodes <= 0) return 0;
-    // ordered merge-join of the two node lists (the reference's lower_bound walk, ORBmatcher.cc:244-371)
+    // vectors that share no node give the empty result before they are validated
     std::vector<int32_t> pairs;
-    int a = 0, b = 0;
-    while (a < kf_fv->n_nodes && b < f_fv->n_nodes) {
-        if (kf_fv->node_ids[a] == f_fv->node_ids[b]) { pairs.push_back(a); pairs.push_back(b); a++; b++; }
-        else if (kf_fv->node_ids[a] < f_fv->node_ids[b]) a++;
-        else b++;
-    }
+    fv_join(kf_fv->node_ids, kf_fv->n_nodes, f_fv->node_ids, f_fv->n_nodes, pairs);
     if (pairs.empty()) return 0;
-    for (const orbfe_feature_vector* fv : {kf_fv, f_fv}) {
-        if (!fv->node_ids || !fv->offsets || fv->offsets[0] != 0) return ORBFE_E_ARG;
-        for (int i = 0; i < fv->n_nodes; i++)
-            if (fv->offsets[i + 1] < fv->offsets[i] || (i > 0 && fv->node_ids[i] <= fv->node_ids[i - 1]))
-                return ORBFE_E_ARG;
-    }
-    // each frame index must belong to one node only (DBoW2 transform); the per-node threads rely on it
-    std::vector<uint8_t> seen(fn, 0);
-    const int nfi = f_fv->offsets[f_fv->n_nodes];
-    for (int i = 0; i < nfi; i++) {
-        const uint32_t x = f_fv->indices[i];
-        if (x >= (uint32_t)fn || seen[x]) return ORBFE_E_ARG;
-        seen[x] = 1;
-    }
-    const int nki = kf_fv->offsets[kf_fv->n_nodes];
+    if (!fv_shape_ok(kf_fv) || !fv_shape_ok(f_fv)) return ORBFE_E_ARG;
+    if (!fv_indices_unique(f_fv, fn)) return ORBFE_E_ARG;
+    // a KF index may sit in several nodes (only F's "matched" state is per index): in range is enough
+    const int nfi = f_fv->offsets[f_fv->n_nodes], nki = kf_fv->offsets[kf_fv->n_nodes];
     for (int i = 0; i < nki; i++)
         if (kf_fv->indices[i] >= (uint32_t)kf_n) return ORBFE_E_ARG;
     const int npairs = (int)pairs.size() / 2;
@@ -5042,9 +5000,10 @@ int orbfe_search_by_bow(const orbfe_keypoint* kf_keys, const uint8_t* kf_desc, c
                        npairs, ms_ptr<const int>(o_kfoff), ms_ptr<const uint32_t>(o_kfidx), ms_ptr<const int>(o_foff),
                        ms_ptr<const uint32_t>(o_fidx), ms_ptr<const int32_t>(o_kfmp), ms_ptr<const uint32_t>(o_kfdesc),
                        ms_ptr<const uint32_t>(o_fdesc), nnratio, F->two_cams ? F->nleft : -1, ms_ptr<int>(o_src));
-    hipLaunchKernelGGL(k_bow_commit, dim3(1), dim3(1024), 0, s, ms_ptr<const OrbKeyPoint>(o_kfkeys),
-                       ms_ptr<const OrbKeyPoint>(o_fkeys), fn, ms_ptr<const int32_t>(o_kfmp), checkOri,
-                       ms_ptr<const int>(o_src), ms_ptr<int>(o_out), ms_ptr<int>(o_result));
+    hipLaunchKernelGGL((k_bow_commit<false, AngKeys, AngKeys>), dim3(1), dim3(1024), 0, s,
+                       AngKeys{ms_ptr<const OrbKeyPoint>(o_fkeys)}, AngKeys{ms_ptr<const OrbKeyPoint>(o_kfkeys)}, fn,
+                       ms_ptr<const int32_t>(o_kfmp), checkOri, ms_ptr<const int>(o_src), ms_ptr<int>(o_out),
+                       ms_ptr<int>(o_result));
     HIPCHK(hipGetLastError());
     timer.end();
     int nm = 0;
@@ -5058,16 +5017,9 @@ int orbfe_keyframe_create(const orbfe_frame* KF, const orbfe_feature_vector* fv,
     *out = nullptr;
     if (!KF || !fv || KF->n < 0 || fv->n_nodes < 0 || (KF->n > 0 && (!KF->keys || !KF->desc))) return ORBFE_E_ARG;
     const int n = KF->n, nn = fv->n_nodes;
-    if (nn > 0) {   // orbfe_search_by_bow's checks of a FeatureVector
-        if (!fv->node_ids || !fv->offsets || fv->offsets[0] != 0) return ORBFE_E_ARG;
-        for (int i = 0; i < nn; i++)
-            if (fv->offsets[i + 1] < fv->offsets[i] || (i > 0 && fv->node_ids[i] <= fv->node_ids[i - 1]))
-                return ORBFE_E_ARG;
-    }
+    bool repeats = false;   // an index in several nodes is accepted here and refused by the KF-KF search
+    if (nn > 0 && (!fv_shape_ok(fv) || !fv_indices_unique(fv, n, &repeats))) return ORBFE_E_ARG;
     const int nki = nn > 0 ? fv->offsets[nn] : 0;
-    if (nki > 0 && !fv->indices) return ORBFE_E_ARG;
-    for (int i = 0; i < nki; i++)
-        if (fv->indices[i] >= (uint32_t)n) return ORBFE_E_ARG;
     auto a16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t o_off = a16((size_t)nn * 4), o_idx = o_off + a16((size_t)(nn + 1) * 4);
     const size_t o_ang = o_idx + a16((size_t)nki * 4), o_desc = o_ang + a16((size_t)n * 4);
@@ -5082,13 +5034,7 @@ int orbfe_keyframe_create(const orbfe_frame* KF, const orbfe_feature_vector* fv,
         *out = kf.release();
         return ORBFE_OK;
     }
-    {
-        std::vector<uint8_t> seen(n, 0);
-        for (int i = 0; i < nki; i++) {
-            if (seen[fv->indices[i]]) kf->unique = false;
-            seen[fv->indices[i]] = 1;
-        }
-    }
+    kf->unique = !repeats;
     kf->bow = nki > 0;   // an empty FeatureVector: SearchByBoW's row is empty, the angles still serve SearchByProjection
     kf->nvec = (int)(total / 16);
     kf->o_off = (int)o_off;
@@ -5155,19 +5101,8 @@ int orbfe_search_by_bow_batch(const orbfe_keyframe* const* kfs, const int32_t* c
     for (size_t i = 0; i < (size_t)n_kfs * fn; i++) out[i] = -1;
     t_bow_batch[1] = n_kfs;   // the rows above are the result of a call that ends before the launch
     if (fn == 0 || fnn == 0 || !any) return ORBFE_OK;
-    if (!f_fv->node_ids || !f_fv->offsets || f_fv->offsets[0] != 0) return ORBFE_E_ARG;
-    for (int i = 0; i < fnn; i++)
-        if (f_fv->offsets[i + 1] < f_fv->offsets[i] || (i > 0 && f_fv->node_ids[i] <= f_fv->node_ids[i - 1]))
-            return ORBFE_E_ARG;
-    // each frame index must belong to one node only (DBoW2 transform); the per-node quads rely on it
+    if (!fv_shape_ok(f_fv) || !fv_indices_unique(f_fv, fn)) return ORBFE_E_ARG;
     const int nfi = f_fv->offsets[fnn];
-    if (nfi > 0 && !f_fv->indices) return ORBFE_E_ARG;
-    std::vector<uint8_t> seen(fn, 0);
-    for (int i = 0; i < nfi; i++) {
-        const uint32_t x = f_fv->indices[i];
-        if (x >= (uint32_t)fn || seen[x]) return ORBFE_E_ARG;
-        seen[x] = 1;
-    }
     if (nfi == 0) return ORBFE_OK;
     if ((size_t)n_kfs * fn + (size_t)n_kfs > ((size_t)1 << 28)) return ORBFE_E_CAPACITY;
     int dev = 0;
@@ -5207,13 +5142,7 @@ int orbfe_search_by_bow_batch(const orbfe_keyframe* const* kfs, const int32_t* c
             nlive++;
             continue;
         }
-        // ordered merge-join of the two node lists, as orbfe_search_by_bow
-        int a = 0, b = 0;
-        while (a < k->nn && b < fnn) {
-            if (k->node_ids[a] == f_fv->node_ids[b]) { pairs[c].push_back(a); pairs[c].push_back(b); a++; b++; }
-            else if (k->node_ids[a] < f_fv->node_ids[b]) a++;
-            else b++;
-        }
+        fv_join(k->node_ids.data(), k->nn, f_fv->node_ids, fnn, pairs[c]);
         cd.mode = pairs[c].empty() ? 1 : 2;
         if (cd.mode == 2) o_pairs[c] = p.upload(pairs[c].data(), pairs[c].size() * 4);
     }
@@ -5245,9 +5174,9 @@ int orbfe_search_by_bow_batch(const orbfe_keyframe* const* kfs, const int32_t* c
                            (const uint32_t*)(k->pack + k->o_idx), ms_ptr<const int>(o_foff),
                            ms_ptr<const uint32_t>(o_fidx), ms_ptr<const int32_t>(o_mp[c]),
                            (const uint32_t*)(k->pack + k->o_desc), d_fdesc, nnratio, nleft, ms_ptr<int>(o_src[c]));
-        hipLaunchKernelGGL(k_bow_commit_ang, dim3(1), dim3(1024), 0, s, (const float*)(k->pack + k->o_ang), d_fkeys, fn,
-                           ms_ptr<const int32_t>(o_mp[c]), checkOri, ms_ptr<const int>(o_src[c]),
-                           d_out + (size_t)c * fn, d_nm + c);
+        hipLaunchKernelGGL((k_bow_commit<false, AngKeys, AngFlat>), dim3(1), dim3(1024), 0, s, AngKeys{d_fkeys},
+                           AngFlat{(const float*)(k->pack + k->o_ang)}, fn, ms_ptr<const int32_t>(o_mp[c]), checkOri,
+                           ms_ptr<const int>(o_src[c]), d_out + (size_t)c * fn, d_nm + c);
     }
     // one workgroup per candidate; the dynamic LDS is the largest fitting candidate's. A batch whose
     // candidates all took the multi-launch path still runs it for the empty rows (no LDS then).

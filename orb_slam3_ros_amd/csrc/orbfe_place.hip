@@ -34,16 +34,11 @@ __host__ __device__ inline size_t kf_bow_batch_lds(int nvec1, int n1, int nvec2,
            (((size_t)n2 + 15) & ~(size_t)15);
 }
 
-// SearchByBoW(KF1, KF2[c]) in one workgroup per candidate c. k_bow_batch's structure, restated for the
-// keyframe-to-keyframe rules: one quad of lanes per KF1 node, the KF2 node found by binary search of
-// KF2's node ids, the node's KF1 features walked in the FeatureVector's stored order, the quad's lanes
-// over the node's KF2 features (lane l: positions l, l + 4, ...). The quad minimum of (dist, position)
-// keys is the reference's first best and the second minimum its bestDist2. A KF2 index belongs to one
-// node only (checked at create), so vbMatched2 is private to the quad: a register mask for nodes of at
-// most 16 KF2 features, a byte per index in LDS beyond. The rules (ORBmatcher.cc:790-860): a KF1
-// feature without map point or at an index >= lim1 is skipped; a KF2 feature without map point,
-// already matched or at an index >= lim2 is neither best nor second best; a match needs
-// bestDist1 < TH_LOW (strict) and float(bestDist1) < nnratio * float(bestDist2).
+// SearchByBoW(KF1, KF2[c]) in one workgroup per candidate c: both packs, both handle arrays and the
+// match state staged in LDS; one quad of lanes per KF1 node, its KF2 node found by binary search of
+// KF2's node ids; the node walked by bow_walk_node under BowRulesKfKf (a KF2 index belongs to one node
+// only, checked at create, so vbMatched2 is private to the quad); the row vpMatches12[idx1] =
+// mp2[bestIdx2] committed in the block; nm[c] written last and read after a stream synchronisation.
 __global__ __launch_bounds__(MT_BOW_NT) void k_bow_kfkf_batch(KfBowBatchIn in) {
     extern __shared__ __attribute__((aligned(16))) uint8_t kb_sm[];
     __shared__ int s_hist[MT_HISTO];
@@ -92,13 +87,7 @@ __global__ __launch_bounds__(MT_BOW_NT) void k_bow_kfkf_batch(KfBowBatchIn in) {
     const uint4* s_d2 = (const uint4*)((const uint8_t*)s_p2 + cd.o_desc);
     const int* s_mp1 = (const int*)s_mp1w;
     const int* s_mp2 = (const int*)s_mp2w;
-    const int lim1 = in.k1.lim, lim2 = cd.lim;
-    const int sl = tid & 3;
-    auto quad_min64 = [](unsigned long long v) {
-        v = mt_min64_dpp_step<0xB1>(v);
-        return mt_min64_dpp_step<0x4E>(v);
-    };
-    constexpr int FQ = 4;   // KF2 features per lane held in registers (nodes of <= 16 KF2 features)
+    const BowRulesKfKf rules{s_mp1, s_mp2, s_m12, s_taken, in.k1.lim, cd.lim, in.nnratio};
     for (int a = tid >> 2; a < in.k1.nn; a += MT_BOW_NT / 4) {
         const unsigned id = s_nid1[a];
         int b = 0, hi = cd.nn;   // lower_bound of the node id among KF2's (the quad's lanes agree)
@@ -108,145 +97,13 @@ __global__ __launch_bounds__(MT_BOW_NT) void k_bow_kfkf_batch(KfBowBatchIn in) {
             else hi = mid;
         }
         if (b >= cd.nn || s_nid2[b] != id) continue;
-        const int b0 = s_o2[b], b1 = s_o2[b + 1];
-        const int a0 = s_o1[a], a1 = s_o1[a + 1];
-        if (b1 - b0 <= 4 * FQ) {
-            // the node's KF2 features in registers (position p = 4 q + lane: the reference's order); the
-            // mask holds the excluded and the matched ones alike
-            uint4 e0[FQ], e1[FQ];
-            int idx2[FQ];
-            unsigned taken = 0u;
-#pragma unroll
-            for (int q = 0; q < FQ; q++) {
-                const int ib = b0 + sl + 4 * q;
-                idx2[q] = ib < b1 ? s_i2[ib] : 0;
-                if (ib < b1 && idx2[q] < lim2 && s_mp2[idx2[q]] >= 0) {
-                    e0[q] = s_d2[2 * idx2[q]];
-                    e1[q] = s_d2[2 * idx2[q] + 1];
-                } else {
-                    e0[q] = e1[q] = make_uint4(0u, 0u, 0u, 0u);
-                    taken |= 1u << q;
-                }
-            }
-            for (int ia = a0; ia < a1; ia++) {
-                const int idx1 = s_i1[ia];
-                if (idx1 >= lim1 || s_mp1[idx1] < 0) continue;
-                const uint4 k0 = s_d1[2 * idx1], k1 = s_d1[2 * idx1 + 1];
-                unsigned long long m_b1 = ~0ull, m_b2 = ~0ull;
-#pragma unroll
-                for (int q = 0; q < FQ; q++) {
-                    if ((taken >> q) & 1u) continue;
-                    const int dist = __popc(k0.x ^ e0[q].x) + __popc(k0.y ^ e0[q].y) + __popc(k0.z ^ e0[q].z) +
-                                     __popc(k0.w ^ e0[q].w) + __popc(k1.x ^ e1[q].x) + __popc(k1.y ^ e1[q].y) +
-                                     __popc(k1.z ^ e1[q].z) + __popc(k1.w ^ e1[q].w);
-                    const unsigned long long key = ((unsigned long long)dist << 32) | (unsigned)(4 * q + sl);
-                    if (key < m_b1) { m_b2 = m_b1; m_b1 = key; }
-                    else if (key < m_b2) m_b2 = key;
-                }
-                const unsigned long long m1 = quad_min64(m_b1);
-                const unsigned long long m2 = quad_min64(m_b1 == m1 ? m_b2 : m_b1);
-                const int bestDist1 = m1 != ~0ull ? (int)(m1 >> 32) : 256;
-                const int bestDist2 = m2 != ~0ull ? (int)(m2 >> 32) : 256;
-                if (bestDist1 < MT_TH_LOW && static_cast<float>(bestDist1) < in.nnratio * static_cast<float>(bestDist2)) {
-                    const int w = (int)(m1 & 0xFFFFFFFFu);   // the winning position
-#pragma unroll
-                    for (int q = 0; q < FQ; q++) {
-                        if (w == 4 * q + sl) {
-                            taken |= 1u << q;
-                            s_m12[idx1] = idx2[q];
-                        }
-                    }
-                }
-            }
-            continue;
-        }
-        // larger nodes: the KF2 features and their flags read from LDS per KF1 feature
-        for (int ia = a0; ia < a1; ia++) {
-            const int idx1 = s_i1[ia];
-            if (idx1 >= lim1 || s_mp1[idx1] < 0) continue;
-            const uint4 k0 = s_d1[2 * idx1], k1 = s_d1[2 * idx1 + 1];
-            unsigned long long m_b1 = ~0ull, m_b2 = ~0ull;
-            for (int ib = b0 + sl; ib < b1; ib += 4) {
-                const int i2 = s_i2[ib];
-                if (i2 >= lim2 || s_mp2[i2] < 0 || s_taken[i2]) continue;
-                const uint4 f0 = s_d2[2 * i2], f1 = s_d2[2 * i2 + 1];
-                const int dist = __popc(k0.x ^ f0.x) + __popc(k0.y ^ f0.y) + __popc(k0.z ^ f0.z) + __popc(k0.w ^ f0.w) +
-                                 __popc(k1.x ^ f1.x) + __popc(k1.y ^ f1.y) + __popc(k1.z ^ f1.z) + __popc(k1.w ^ f1.w);
-                const unsigned long long key = ((unsigned long long)dist << 32) | (unsigned)ib;
-                if (key < m_b1) { m_b2 = m_b1; m_b1 = key; }
-                else if (key < m_b2) m_b2 = key;
-            }
-            const unsigned long long m1 = quad_min64(m_b1);
-            const unsigned long long m2 = quad_min64(m_b1 == m1 ? m_b2 : m_b1);
-            if (sl == 0) {
-                const int bestDist1 = m1 != ~0ull ? (int)(m1 >> 32) : 256;
-                const int bestDist2 = m2 != ~0ull ? (int)(m2 >> 32) : 256;
-                if (bestDist1 < MT_TH_LOW && static_cast<float>(bestDist1) < in.nnratio * static_cast<float>(bestDist2)) {
-                    const int bestIdx2 = s_i2[(int)(m1 & 0xFFFFFFFFu)];
-                    s_m12[idx1] = bestIdx2;
-                    s_taken[bestIdx2] = 1;
-                }
-            }
-            WAVE_SYNC();   // the quad's next KF1 feature sees the matched KF2 feature
-        }
+        bow_walk_node(s_o1[a], s_o1[a + 1], s_o2[b], s_o2[b + 1], s_i1, s_i2, s_d1, s_d2, tid & 3, rules);
     }
     SYNC();
-    // rotation consistency (ORBmatcher.cc:862-900) and the output row: vpMatches12[idx1] = mp2[bestIdx2]
-    int sidx[MT_BOW_FR], bin[MT_BOW_FR];
-#pragma unroll
-    for (int u = 0; u < MT_BOW_FR; u++) {
-        const int i = tid + u * MT_BOW_NT;
-        sidx[u] = i < n1 ? s_m12[i] : -1;
-        bin[u] = sidx[u] >= 0 ? mt_rot_bin(s_ang1[i], s_ang2[sidx[u]]) : 0;
-        if (sidx[u] >= 0 && in.checkOri) atomicAdd(&s_hist[bin[u]], 1);
-    }
-    SYNC();
-    if (tid == 0) s_keep = in.checkOri ? mt_three_maxima_keep(s_hist) : 0xFFFFFFFFu;
-    SYNC();
-    int cnt = 0;
-#pragma unroll
-    for (int u = 0; u < MT_BOW_FR; u++) {
-        const int i = tid + u * MT_BOW_NT;
-        if (i >= n1) continue;
-        int o = -1;
-        if (sidx[u] >= 0 && (!in.checkOri || ((s_keep >> bin[u]) & 1u))) o = s_mp2[sidx[u]];
-        out[i] = o;
-        cnt += o >= 0 ? 1 : 0;
-    }
-    atomicAdd(&s_n, cnt);
+    bow_commit_rows<true>(n1, s_m12, [&](int, int i) { return s_ang1[i]; }, AngFlat{s_ang2}, s_mp2, in.checkOri, out,
+                          s_hist, &s_keep, &s_n);
     SYNC();
     if (tid == 0) in.nm[c] = s_n;   // the host reads the rows after a stream synchronisation
-}
-
-// k_bow_kfkf_commit for two resident keyframes (the packs keep the angles only): the multi-launch path
-// of a batch candidate that does not fit one workgroup
-__global__ __launch_bounds__(1024) void k_bow_kfkf_commit_ang(const float* ang1, const float* ang2, int n1,
-                                                              const int32_t* mp2, int checkOri, const int* out_idx,
-                                                              int* out12, int* result) {
-    __shared__ int s_hist[MT_HISTO];
-    __shared__ unsigned s_keep;
-    __shared__ int s_n;
-    if (threadIdx.x < MT_HISTO) s_hist[threadIdx.x] = 0;
-    if (threadIdx.x == 0) s_n = 0;
-    SYNC();
-    for (int i = threadIdx.x; i < n1; i += blockDim.x) {
-        const int j = out_idx[i];
-        if (j >= 0 && checkOri) atomicAdd(&s_hist[mt_rot_bin(ang1[i], ang2[j])], 1);
-    }
-    SYNC();
-    if (threadIdx.x == 0) s_keep = checkOri ? mt_three_maxima_keep(s_hist) : 0xFFFFFFFFu;
-    SYNC();
-    int cnt = 0;
-    for (int i = threadIdx.x; i < n1; i += blockDim.x) {
-        const int j = out_idx[i];
-        int o = -1;
-        if (j >= 0 && (!checkOri || ((s_keep >> mt_rot_bin(ang1[i], ang2[j])) & 1u))) o = mp2[j];
-        out12[i] = o;
-        cnt += o >= 0 ? 1 : 0;
-    }
-    atomicAdd(&s_n, cnt);
-    SYNC();
-    if (threadIdx.x == 0) result[0] = s_n;
 }
 
 namespace {
@@ -308,13 +165,7 @@ int orbfe_search_by_bow_kf_batch(const orbfe_keyframe* kf1, const int32_t* mp1, 
         memset(&cd, 0, sizeof(cd));
         cd.mode = 1;
         if (!k || !k->bow) continue;
-        // ordered merge-join of the two node lists, as orbfe_search_by_bow_kf2
-        int a = 0, b = 0;
-        while (a < kf1->nn && b < k->nn) {
-            if (kf1->node_ids[a] == k->node_ids[b]) { pairs[c].push_back(a); pairs[c].push_back(b); a++; b++; }
-            else if (kf1->node_ids[a] < k->node_ids[b]) a++;
-            else b++;
-        }
+        fv_join(kf1->node_ids.data(), kf1->nn, k->node_ids.data(), k->nn, pairs[c]);
         if (pairs[c].empty()) continue;
         o_mp2[c] = p.upload(mp2[c], (size_t)k->n * 4);
         cd = side(k, nleft2 ? nleft2[c] : -1);
@@ -361,9 +212,10 @@ int orbfe_search_by_bow_kf_batch(const orbfe_keyframe* kf1, const int32_t* mp1, 
                            ms_ptr<const int32_t>(o_mp2[c]), (const uint32_t*)(kf1->pack + kf1->o_desc),
                            (const uint32_t*)(k->pack + k->o_desc), nnratio, ms_ptr<int>(o_m2[c]), ms_ptr<int>(o_oi[c]),
                            lim1, cands[c].lim);
-        hipLaunchKernelGGL(k_bow_kfkf_commit_ang, dim3(1), dim3(1024), 0, s, (const float*)(kf1->pack + kf1->o_ang),
-                           (const float*)(k->pack + k->o_ang), n1, ms_ptr<const int32_t>(o_mp2[c]), checkOri,
-                           ms_ptr<const int>(o_oi[c]), d_out + (size_t)c * n1, d_nm + c);
+        hipLaunchKernelGGL((k_bow_commit<true, AngFlat, AngFlat>), dim3(1), dim3(1024), 0, s,
+                           AngFlat{(const float*)(kf1->pack + kf1->o_ang)}, AngFlat{(const float*)(k->pack + k->o_ang)},
+                           n1, ms_ptr<const int32_t>(o_mp2[c]), checkOri, ms_ptr<const int>(o_oi[c]),
+                           d_out + (size_t)c * n1, d_nm + c);
     }
     // one workgroup per candidate; the dynamic LDS is the largest fitting candidate's. A batch whose
     // live candidates all took the multi-launch path still runs it for the empty rows (no LDS then).

@@ -13,7 +13,7 @@ kind "kfkf": side a = KF1, side b = KF2 (a.nleft / b.nleft: NLeft); slots are KF
 
 pad_frame / pad_keyframe append inert features to side b / side a (features in no node, and features with
 map point -1 in nodes the other side does not have) until the one-workgroup forms no longer fit; the sizes
-come from the drivers' own bounds, restated in block_lds / batch_lds.
+come from the drivers' own bounds, restated in block_lds / batch_lds / kf_batch_lds.
 """
 import numpy as np
 
@@ -596,12 +596,24 @@ def block_lds(da, db, npairs):
     return _a(sum(_a(u, 256) for u in ups) + bn * 32, 16) + bn * 4 + 16
 
 
+def _pack(d):
+    """Bytes of orbfe_keyframe_create's pack: node ids, CSR offsets, CSR indices, angles, descriptors."""
+    n, nn, ni = d
+    return _a(nn * 4, 16) + _a((nn + 1) * 4, 16) + _a(ni * 4, 16) + _a(n * 4, 16) + n * 32
+
+
 def batch_lds(da, db):
     """bow_batch_lds + 16 of candidate a against frame b (orbfe_keyframe_create's pack layout)."""
     (an, ann, ai), (bn, bnn, bi) = da, db
     nvec_fm = _a(_a(bnn * 4, 256) + _a((bnn + 1) * 4, 256) + bi * 4, 16) // 16
-    pack = _a(ann * 4, 16) + _a((ann + 1) * 4, 16) + _a(ai * 4, 16) + _a(an * 4, 16) + an * 32
-    return (nvec_fm + 2 * bn + pack // 16 + (an + 3) // 4) * 16 + bn * 4 + 16
+    return (nvec_fm + 2 * bn + _pack(da) // 16 + (an + 3) // 4) * 16 + bn * 4 + 16
+
+
+def kf_batch_lds(da, db):
+    """kf_bow_batch_lds + 16 of KF1 a against candidate b: both packs, both handle arrays, 4 bytes per KF1
+    feature and a byte per KF2 feature."""
+    an, bn = da[0], db[0]
+    return (_pack(da) // 16 + _pack(db) // 16 + (an + 3) // 4 + (bn + 3) // 4) * 16 + an * 4 + _a(bn, 16) + 16
 
 
 def fits_block(da, db, npairs):
@@ -610,6 +622,10 @@ def fits_block(da, db, npairs):
 
 def fits_batch(da, db):
     return batch_lds(da, db) <= LDS_MAX and db[0] <= F_MAX
+
+
+def fits_kf_batch(da, db):
+    return kf_batch_lds(da, db) <= LDS_MAX and da[0] <= F_MAX
 
 
 def _npairs(case):
