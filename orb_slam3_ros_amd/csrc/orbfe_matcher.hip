@@ -2862,9 +2862,12 @@ __global__ __launch_bounds__(MT_INIT_WNT) void k_init_eval(FrameDev f1, FrameDev
         if (cx0 >= ORBFE_GRID_COLS || cx1 < 0 || cy0 >= ORBFE_GRID_ROWS || cy1 < 0) cx1 = cx0 - 1;
     }
     const bool bCheckLevels = (level1 > 0) || (level1 >= 0);
-    // only level-0 queries search: the octave-0 grid (pcstart) holds exactly the level-0 candidates
-    const int* cs = f2.pcstart;
-    const int* ci = f2.pcidx;
+    // A level-0 query reads the level grid (pcstart: octaves -1 and 0, the filter below leaves octave 0).
+    // A negative octave applies no level filter in the reference: every key of F2 is a candidate, so
+    // such a query walks the full grid, which the host builds only when F1 has one (f2.cstart is not
+    // filled otherwise, and no query reads it). The CSR position orders one query's candidates only.
+    const int* cs = level1 < 0 ? f2.cstart : f2.pcstart;
+    const int* ci = level1 < 0 ? f2.cidx : f2.pcidx;
     unsigned long long b1 = ~0ull, b2 = ~0ull;
     for (int ix = cx0 + sl; ix <= cx1; ix += 16) {
         const int j1 = cs[ix * ORBFE_GRID_ROWS + cy1 + 1];
@@ -4807,7 +4810,7 @@ int orbfe_search_by_projection_kf_batch(const orbfe_frame* cur, const orbfe_keyf
 }
 
 static int sfi_core(const orbfe_frame* F1, const orbfe_frame* F2, float* prev_matched, int32_t* matches12,
-                    int32_t windowSize, float nnratio, int32_t checkOri);
+                    int32_t windowSize, float nnratio, int32_t checkOri, bool all_levels);
 
 int orbfe_search_for_initialization(const orbfe_frame* F1, const orbfe_frame* F2, float* prev_matched,
                                     int32_t* matches12, int32_t windowSize, float nnratio, int32_t checkOri) {
@@ -4816,12 +4819,12 @@ int orbfe_search_for_initialization(const orbfe_frame* F1, const orbfe_frame* F2
     // windows read F2's level-0 features only (GetFeaturesInArea(.., level1, level1)). The call runs
     // on those two subsets (order-preserving, so "earlier query" and the enumeration order are
     // unchanged) and scatters the results back: a fifth of the monocular initialiser's 5 x nFeatures
-    // to pack, upload and grid. A negative octave (no level filter in the reference) keeps the
-    // whole frames.
+    // to pack, upload and grid. A negative octave (no level filter in the reference: its window
+    // reads every level of F2) keeps the whole frames and F2's full grid beside the level grid.
     bool neg = false;
     for (int i = 0; i < F1->n && !neg; i++) neg = F1->keys[i].octave < 0;
     if (neg || F1->n == 0 || F2->n == 0)
-        return sfi_core(F1, F2, prev_matched, matches12, windowSize, nnratio, checkOri);
+        return sfi_core(F1, F2, prev_matched, matches12, windowSize, nnratio, checkOri, neg);
     std::vector<int32_t> i1, i2;
     for (int i = 0; i < F1->n; i++)
         if (F1->keys[i].octave == 0) i1.push_back(i);
@@ -4845,7 +4848,7 @@ int orbfe_search_for_initialization(const orbfe_frame* F1, const orbfe_frame* F2
     c1.n = m1; c1.keys = k1.data(); c1.desc = d1.data(); c1.uright = nullptr;
     c2.n = m2; c2.keys = k2.data(); c2.desc = d2.data(); c2.uright = nullptr;
     std::vector<int32_t> mc((size_t)std::max(m1, 1));
-    const int r = sfi_core(&c1, &c2, pv.data(), mc.data(), windowSize, nnratio, checkOri);
+    const int r = sfi_core(&c1, &c2, pv.data(), mc.data(), windowSize, nnratio, checkOri, false);
     if (r < 0) return r;
     for (int i = 0; i < F1->n; i++) matches12[i] = -1;
     for (int j = 0; j < m1; j++) {
@@ -4857,7 +4860,7 @@ int orbfe_search_for_initialization(const orbfe_frame* F1, const orbfe_frame* F2
 }
 
 static int sfi_core(const orbfe_frame* F1, const orbfe_frame* F2, float* prev_matched, int32_t* matches12,
-                    int32_t windowSize, float nnratio, int32_t checkOri) {
+                    int32_t windowSize, float nnratio, int32_t checkOri, bool all_levels) {
     const int n1 = F1->n;
     if (n1 == 0) return 0;
     if (F2->n == 0) {
@@ -4871,7 +4874,8 @@ static int sfi_core(const orbfe_frame* F1, const orbfe_frame* F2, float* prev_ma
     const size_t o_prev = p.upload(prev_matched, (size_t)n1 * 8);
     f1p.cstart = f1p.cidx = 0;
     f2p.plan_grid(p, 2);
-    f2p.gfirst = 1;   // k_init_eval reads the octave-0 grid only
+    // k_init_eval reads the level grid, and the full grid for queries with a negative octave
+    f2p.gfirst = all_levels ? 0 : 1;
     const size_t o_assign = p.scratch((size_t)n1 * 4);
     const size_t o_adist = p.scratch((size_t)n1 * 4);
     const size_t o_skey = p.scratch((size_t)n1 * 4);
