@@ -332,26 +332,28 @@ def ratio_cases(th, nnratio):
 
 # ---------------------------------------------------------------- stereo
 def stereo_edge(kind, th):
-    """er == radius exactly stays (the rule is er > radius), one float over goes; uR of 0 and -1 skip the test."""
+    """er == radius exactly stays (the rule is er > radius), one float over goes; uR of 0 and -1 skip the test
+    (the rule is uR > 0), the smallest positive float applies it (far from the predicted uR: removed)."""
     s = Scene(kind, th, stereo=True)
     R = s.R(0)
     exp = []
-    for j, mode in enumerate(("eq", "over", "zero", "minus")):
+    for j, mode in enumerate(("eq", "over", "zero", "minus", "tiny")):
         b = base_desc(90 + j)
-        u, v = f32(150.0 + 150 * j), f32(200.0)
+        u, v = f32(150.0 + 150 * (j % 4)), f32(200.0 + 150 * (j // 4))
         pur = f32(100.0) if kind == "local" else sd.py_ur(u, MBF, 0.5)   # the point's predicted uR
-        ur = {"eq": f32(pur - R), "over": down(f32(pur - R)), "zero": f32(0.0), "minus": f32(-1.0)}[mode]
+        ur = {"eq": f32(pur - R), "over": down(f32(pur - R)), "zero": f32(0.0), "minus": f32(-1.0),
+              "tiny": np.nextafter(f32(0.0), f32(1.0))}[mode]
         if mode == "eq":
             assert abs(f32(pur - ur)) == R
-        if mode == "over":
-            assert abs(f32(pur - ur)) > R
+        if mode in ("over", "tiny"):
+            assert ur > 0 and abs(f32(pur - ur)) > R
         exp.append((s.query(u, v, 0, b, xr=pur), s.kp(u, v, 0, flip(b, 5), ur=ur), mode))
 
     def check(case, tr, mvp, n):
         for qi, kp, mode in exp:
-            assert rules_of(tr, qi)[kp] == ("uR" if mode == "over" else "best"), mode
-            assert mvp[kp] == (-1 if mode == "over" else case.q["id"][qi])
-        assert n == 3
+            assert rules_of(tr, qi)[kp] == ("uR" if mode in ("over", "tiny") else "best"), mode
+            assert mvp[kp] == (-1 if mode in ("over", "tiny") else case.q["id"][qi])
+        assert n == 3 and {m for _, _, m in exp} >= {"zero", "minus", "tiny"}
     return s.case("stereo-edge", "uR > 0 and er > radius", check)
 
 

@@ -1,0 +1,918 @@
+"""Planted two-camera SearchByProjection scenes (Frame.Nleft != -1): every rule of the local-map form
+(ORBmatcher.cc:43-213, kind "local2") and of the last-frame form (:1695-1884, kind "lastframe2") at the value
+where it decides. Each case names its rule and carries
+  expect / n   the hand-derived mvpMapPoints and return value,
+  check        `check(case, trace)`: proves from the trace of oracle/sbp_definition.py that this rule decided,
+  variant      the wrong readings of the reference (sbp_definition's `variant=`) that must answer differently,
+  ths          local2: the th values at which the same expectation holds (th scales only the left radius).
+
+Keypoints are named by handles ("L", i) / ("R", j) while a scene is built; `case.g(handle)` is the global row
+(left rows [0, nleft), right rows [nleft, n)). Descriptors are planted as in sbp_patterns: a query's candidates
+are its own descriptor with d chosen bits flipped. Points that must not interact sit at sites 90 px apart; the
+two cameras have a grid each, so a left and a right site may share coordinates. pad_keys / pad_queries append
+inert right-camera keypoints / inert points up to 2,049 without moving a planted row or nleft.
+"""
+import numpy as np
+
+from oracle import sbp_definition as sd
+from orb_slam3_ros_amd.extractor import KEYPOINT_DTYPE
+from orb_slam3_ros_amd.matcher import MAP_POINT_DTYPE, MP_BAD, MP_IN_VIEW, MP_IN_VIEW_R, PROJ_POINT_DTYPE, MatchFrame
+from sbp_patterns import BOUNDS, MBF, NLEVELS, PAD_N, PLANS, SF, _plan_bins, base_desc, down, flip, up
+
+f32 = np.float32
+QID = 5000
+TH_LF = 7
+
+
+def site(j):
+    return f32(80.0 + 90 * (j % 7)), f32(60.0 + 90 * (j // 7))
+
+
+def rules_of(s):
+    return {i: r for i, r in s["cands"]}
+
+
+class Case2:
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def g(self, h):
+        return h[1] if h[0] == "L" else self.F.nleft + h[1]
+
+    def __repr__(self):
+        return self.name
+
+
+class Scene2:
+    def __init__(self, kind, th, nnratio=0.8, stereo=False, **par):
+        self.kind, self.th, self.nnratio, self.stereo, self.par = kind, th, nnratio, stereo, par
+        self.k = {"L": [], "R": []}
+        self.link, self.held, self.q, self.ruv = {}, {}, [], []
+
+    def kp(self, side, x, y, octave, desc, angle=0.0, held=None, to=None, ur=-1.0):
+        """held: (handle id, observations) in the slot before the search; to: the partner's handle (l2r / r2l)."""
+        self.k[side].append((f32(x), f32(y), octave, f32(angle), desc, f32(ur)))
+        h = (side, len(self.k[side]) - 1)
+        if held is not None:
+            self.held[h] = held
+        if to is not None:
+            self.link[h] = to
+        return h
+
+    def L(self, *a, **kw):
+        return self.kp("L", *a, **kw)
+
+    def Rt(self, *a, **kw):
+        return self.kp("R", *a, **kw)
+
+    def mp(self, desc, left=None, right=None, lvl=0, lvl_r=None, obs=1, cos=0.999, cos_r=0.999, depth=1.0, flags=None):
+        """left / right: (x, y) of the projection into that camera; None: not in that camera's view."""
+        r = np.zeros((), MAP_POINT_DTYPE)
+        if left is not None:
+            r["proj_x"], r["proj_y"] = left
+        if right is not None:
+            r["proj_xr"], r["proj_yr"] = right
+        r["scale_level"], r["scale_level_r"] = lvl, lvl if lvl_r is None else lvl_r
+        r["view_cos"], r["view_cos_r"], r["depth"] = cos, cos_r, depth
+        r["flags"] = (MP_IN_VIEW if left is not None else 0) | (MP_IN_VIEW_R if right is not None else 0) \
+            if flags is None else flags
+        r["observations"], r["id"], r["desc"] = obs, QID + len(self.q), desc
+        self.q.append(r)
+        return len(self.q) - 1
+
+    def pt(self, desc, uv, ruv, octave=0, angle=0.0, obs=1, invzc=0.5, valid=1):
+        r = np.zeros((), PROJ_POINT_DTYPE)
+        r["u"], r["v"], r["invzc"], r["octave"], r["angle"] = uv[0], uv[1], invzc, octave, angle
+        r["valid"], r["observations"], r["id"], r["desc"] = valid, obs, QID + len(self.q), desc
+        self.q.append(r)
+        self.ruv.append((f32(ruv[0]), f32(ruv[1])))
+        return len(self.q) - 1
+
+    def case(self, name, rule, exp, n, check, variant, ths=None):
+        """exp: {handle: query index} of the slots the search leaves written (every other slot keeps its holder)."""
+        rows = self.k["L"] + self.k["R"]
+        nl = len(self.k["L"])
+        k = np.zeros(len(rows), KEYPOINT_DTYPE)
+        d = np.zeros((len(rows), 32), np.uint8)
+        for i, (x, y, o, a, de, _) in enumerate(rows):
+            k["x"][i], k["y"][i], k["octave"][i], k["angle"][i], d[i] = x, y, o, a, de
+        k["size"] = 31.0 * SF[k["octave"]]
+        k["response"], k["class_id"] = 20.0, -1
+        g = lambda h: h[1] if h[0] == "L" else nl + h[1]   # noqa: E731
+        l2r, r2l = np.full(nl, -1, np.int32), np.full(len(rows) - nl, -1, np.int32)
+        for h, to in self.link.items():
+            assert h[0] != to[0]
+            (l2r if h[0] == "L" else r2l)[h[1]] = to[1]
+        ur = np.array([r[5] for r in rows], np.float32) if self.stereo else None
+        F = MatchFrame(k, d, BOUNDS, SF, ur, MBF, nleft=nl, l2r=l2r, r2l=r2l)
+        mvp0, obs = np.full(F.N, -1, np.int32), np.zeros(F.N, np.int32)
+        for h, (hid, o) in self.held.items():
+            mvp0[g(h)], obs[g(h)] = hid, o
+        expect = mvp0.copy()
+        for h, qi in exp.items():
+            expect[g(h)] = -1 if qi is None else QID + qi
+        dt = MAP_POINT_DTYPE if self.kind == "local2" else PROJ_POINT_DTYPE
+        par = dict(th=self.th, nnratio=self.nnratio, fw=False, bw=False, check_ori=False, bfar=False, thfar=50.0)
+        par.update(self.par)
+        assert F.N <= 300 and len(self.q) <= 300, name
+        return Case2(name=f"{name}-{self.kind}", rule=rule, kind=self.kind, F=F, q=np.array(self.q, dt),
+                     ruv=np.array(self.ruv, np.float32).reshape(-1, 2) if self.kind == "lastframe2" else None,
+                     mvp0=mvp0, obs=obs, expect=expect, n=n, check=check,
+                     variant=(variant,) if isinstance(variant, str) else tuple(variant), par=par,
+                     ths=tuple(ths) if ths else (self.th,))
+
+
+# ================================================================ local map
+def four_writes():
+    """A point with a partner on either side writes four slots; one without writes two."""
+    s = Scene2("local2", 1)
+    b = base_desc(300)
+    (x, y), (x1, y1), far = site(0), site(1), site(20)
+    Rp = s.Rt(far[0], far[1], 3, base_desc(301))
+    Lp = s.L(far[0], far[1], 3, base_desc(302))
+    La = s.L(x, y, 0, flip(b, 5), to=Rp)
+    Rb = s.Rt(x, y, 0, flip(b, 3), to=Lp)
+    q0 = s.mp(b, (x, y), (x, y))
+    b1 = base_desc(303)
+    Lc, Rc = s.L(x1, y1, 0, flip(b1, 5)), s.Rt(x1, y1, 0, flip(b1, 3))
+    q1 = s.mp(b1, (x1, y1), (x1, y1))
+
+    def check(c, tr):
+        assert [w[:2] for w in tr["q"][q0]["writes"]] == [[0, c.g(La)], [1, c.g(Rp)], [2, c.g(Lp)], [3, c.g(Rb)]]
+        assert [w[:2] for w in tr["q"][q1]["writes"]] == [[0, c.g(Lc)], [3, c.g(Rc)]]
+    return s.case("four-writes", "left best, l2r partner, r2l partner, right best, in this order; each counts",
+                  {La: q0, Rp: q0, Lp: q0, Rb: q0, Lc: q1, Rc: q1}, 6, check, "no-partners", (1, 3))
+
+
+def link_guards():
+    """Partner -1 (no write), the partner is the last row of either camera, and l2r[best] is the row the right
+    search then picks (obs 0: the slot is written twice and r2l writes the left best again: 4 writes, 2 slots)."""
+    s = Scene2("local2", 1)
+    b, b1, b2 = base_desc(310), base_desc(311), base_desc(312)
+    (x, y), (x1, y1), (x2, y2), far = site(0), site(1), site(2), site(20)
+    La = s.L(x, y, 0, flip(b, 5))
+    Rb = s.Rt(x, y, 0, flip(b, 3))
+    q0 = s.mp(b, (x, y), (x, y))
+    Lc = s.L(x1, y1, 0, flip(b1, 5))
+    Rc = s.Rt(x1, y1, 0, flip(b1, 3), to=Lc)
+    s.link[Lc] = Rc
+    q1 = s.mp(b1, (x1, y1), (x1, y1), obs=0)
+    Ld = s.L(x2, y2, 0, flip(b2, 5))
+    Re = s.Rt(x2, y2, 0, flip(b2, 3))
+    q2 = s.mp(b2, (x2, y2), (x2, y2))
+    Llast = s.L(far[0], far[1], 3, base_desc(313))
+    Rlast = s.Rt(far[0], far[1], 3, base_desc(314))
+    s.link[Ld], s.link[Re] = Rlast, Llast
+
+    def check(c, tr):
+        assert c.g(Llast) == c.F.nleft - 1 and c.g(Rlast) == c.F.nleft + len(s.k["R"]) - 1   # the last planted rows
+        assert c.F.l2r[La[1]] == -1 and c.F.r2l[Rb[1]] == -1 and len(tr["q"][q0]["writes"]) == 2
+        assert [w[:2] for w in tr["q"][q1]["writes"]] == [[0, c.g(Lc)], [1, c.g(Rc)], [2, c.g(Lc)], [3, c.g(Rc)]]
+        assert tr["q"][q1]["R"]["best"] == c.g(Rc)
+        assert [w[1] for w in tr["q"][q2]["writes"]] == [c.g(Ld), c.g(Rlast), c.g(Llast), c.g(Re)]
+    return s.case("link-guards", "l2r / r2l: -1 writes nothing; the last row; the partner is the right best itself",
+                  {La: q0, Rb: q0, Lc: q1, Rc: q1, Ld: q2, Re: q2, Llast: q2, Rlast: q2}, 10, check, "count-slots", (1, 3))
+
+
+def partner_overwrites():
+    """A partner slot held with observations > 0 is overwritten; the writer's observations then decide whether a
+    later point finds it free (0) or blocked (> 0). Both directions."""
+    s = Scene2("local2", 1)
+    b, b1 = base_desc(320), base_desc(321)
+    (x, y), (x1, y1), (x2, y2), (x3, y3) = site(0), site(1), site(2), site(3)
+    Rp = s.Rt(x1, y1, 0, flip(b1, 2), held=(77, 3))
+    Rp2 = s.Rt(x1 + f32(1), y1, 1, flip(b1, 30))
+    La = s.L(x, y, 0, flip(b, 5), to=Rp)
+    q0 = s.mp(b, (x, y), None, obs=0)              # overwrites Rp with a holder of 0 observations
+    q1 = s.mp(b1, None, (x1, y1), lvl_r=1)         # finds Rp free
+    b2, b3 = base_desc(322), base_desc(323)
+    Lb = s.L(x3, y3, 0, flip(b3, 2), held=(78, 2))
+    Lb2 = s.L(x3 + f32(1), y3, 1, flip(b3, 30))
+    Rc = s.Rt(x2, y2, 0, flip(b2, 5), to=Lb)
+    q2 = s.mp(b2, None, (x2, y2), obs=2)           # overwrites Lb with a holder of 2 observations
+    q3 = s.mp(b3, (x3, y3), None, lvl=1)           # finds Lb blocked: its second choice
+
+    def check(c, tr):
+        w = tr["q"][q0]["writes"]
+        assert w[1] == [1, c.g(Rp), 77, 3]                      # written over a holder with observations
+        assert tr["q"][q1]["R"]["best"] == c.g(Rp)
+        assert tr["q"][q2]["writes"][0] == [2, c.g(Lb), 78, 2]
+        assert rules_of(tr["q"][q3]["L"])[c.g(Lb)] == "blocked" and tr["q"][q3]["L"]["best"] == c.g(Lb2)
+    return s.case("partner-overwrites", "partner writes test nothing: a held slot is overwritten",
+                  {La: q0, Rp: q1, Rc: q2, Lb: q2, Lb2: q3}, 6, check, "partner-guarded", (1, 3))
+
+
+def last_writer(nw):
+    """nw points write one right slot in turn through their l2r partner writes (the slot is held with
+    observations before the search), their observations alternating and the last one's > 0: a probe after them
+    finds the slot blocked and takes its second choice. The first writer has 0 observations, so a reading that
+    keeps the first writer lets the probe in. nw == 2 adds the other polarity on a second slot (free at the
+    start, last writer 0 observations: the probe takes it)."""
+    s = Scene2("local2", 1)
+    bp = base_desc(330)
+    xp, yp = site(20)
+    R0 = s.Rt(xp, yp, 0, flip(bp, 2), held=(77, 3))
+    R0b = s.Rt(xp + f32(1), yp, 0, flip(bp, 30))
+    ob = [0, 0, 1, 0, 1, 0, 1][-nw:] if nw == 7 else [k % 2 for k in range(nw)]
+    assert ob[0] == 0 and ob[-1] == 1 and len(ob) == nw
+    exp, W = {}, []
+    for k in range(nw):
+        b = base_desc(331 + k)
+        x, y = site(k)
+        Lk = s.L(x, y, 0, flip(b, 5), to=R0)
+        W.append(s.mp(b, (x, y), None, obs=ob[k]))
+        exp[Lk] = W[-1]
+    probe = s.mp(bp, None, (xp, yp))
+    exp[R0], exp[R0b] = W[-1], probe
+    n = 2 * nw + 1
+    probe2 = None
+    if nw == 2:
+        bq = base_desc(340)
+        xq, yq = site(21)
+        R1 = s.Rt(xq, yq, 0, flip(bq, 2))
+        for k, o in enumerate((1, 0)):
+            b = base_desc(341 + k)
+            x, y = site(10 + k)
+            Lk = s.L(x, y, 0, flip(b, 5), to=R1)
+            exp[Lk] = s.mp(b, (x, y), None, obs=o)
+        probe2 = s.mp(bq, None, (xq, yq))
+        exp[R1] = probe2
+        n += 5
+
+    def check(c, tr):
+        writers = [qi for qi, t in tr["q"].items() if any(w[1] == c.g(R0) for w in t["writes"])]
+        assert writers == W and len(W) == nw
+        assert rules_of(tr["q"][probe]["R"])[c.g(R0)] == "blocked" and tr["q"][probe]["R"]["best"] == c.g(R0b)
+        if probe2 is not None:
+            assert tr["q"][probe2]["R"]["bd"] == 2
+    return s.case(f"last-writer-{nw}", "a slot's occupant is its last writer before the entry", exp, n, check,
+                  "first-writer", (1, 3))
+
+
+def own_partner_seen():
+    s = Scene2("local2", 1)
+    exp, Q = {}, []
+    for j, ob in enumerate((3, 0)):
+        b = base_desc(350 + j)
+        x, y = site(j)
+        Ra = s.Rt(x, y, 0, flip(b, 1))
+        Rb = s.Rt(x + f32(1), y, 0, flip(b, 30))
+        La = s.L(x, y, 0, flip(b, 2), to=Ra)
+        s.link[Ra] = La
+        q = s.mp(b, (x, y), (x, y), obs=ob)
+        Q.append((q, Ra, Rb, ob))
+        exp.update({La: q, Ra: q})
+        if ob:
+            exp[Rb] = q
+
+    def check(c, tr):
+        for q, Ra, Rb, ob in Q:
+            t = tr["q"][q]
+            assert t["writes"][1][:2] == [1, c.g(Ra)]
+            assert rules_of(t["R"])[c.g(Ra)] == ("blocked" if ob else "best")
+            assert t["R"]["best"] == c.g(Rb if ob else Ra)
+    return s.case("own-partner-seen", "the right search sees the point's own l2r partner write", exp, 3 + 4, check,
+                  "own-partner-unseen", (1, 3))
+
+
+def left_ratio_cancels():
+    s = Scene2("local2", 1)
+    b = base_desc(360)
+    x, y = site(0)
+    s.L(x, y, 0, flip(b, 20))
+    s.L(x + f32(0.5), y, 0, flip(b, range(256 - 22, 256)))
+    s.Rt(x, y, 0, b)
+    q = s.mp(b, (x, y), (x, y))
+
+    def check(c, tr):
+        t = tr["q"][q]
+        assert (t["L"]["bd"], t["L"]["bd2"], t["L"]["outcome"]) == (20, 22, "ratio")
+        assert t["R"] is None and t["R_skip"] == "left ratio"
+    return s.case("left-ratio-cancels-right", "a failed left ratio test `continue`s past the right search", {}, 0, check,
+                  "ratio-searches-right", (1, 3))
+
+
+def left_far_right_runs():
+    """Left bestDist 101 and an empty left window: the right search still runs. 100 / 101 on both cameras."""
+    s = Scene2("local2", 1)
+    exp, T = {}, []
+    for j, (dl, dr) in enumerate(((101, 5), (None, 5), (100, 101), (101, 100))):
+        b = base_desc(370 + j)
+        x, y = site(j)
+        Lk = s.L(x, y, 0, flip(b, dl)) if dl is not None else None
+        Rk = s.Rt(x, y, 0, flip(b, dr))
+        q = s.mp(b, (x, y), (x, y))
+        T.append((q, dl, dr))
+        if dl is not None and dl <= 100:
+            exp[Lk] = q
+        if dr <= 100:
+            exp[Rk] = q
+
+    def check(c, tr):
+        for q, dl, dr in T:
+            t = tr["q"][q]
+            assert t["L"]["outcome"] == ("empty" if dl is None else "kept" if dl <= 100 else "distance")
+            assert t["R"]["bd"] == dr and t["R"]["outcome"] == ("kept" if dr <= 100 else "distance")
+    return s.case("left-far-right-runs", "bestDist <= TH_HIGH on either camera; a far or empty left does not stop the right",
+                  exp, 4, check, "far-left-stops", (1, 3))
+
+
+def gates():
+    """IN_VIEW only, IN_VIEW_R only, neither, scale_level_r == -1, a bad point, bFar one float past the threshold."""
+    s = Scene2("local2", 1, bfar=True, thfar=20.0)
+    exp, T = {}, []
+    rows = [("in-view", MP_IN_VIEW, 0, 1.0), ("in-view-r", MP_IN_VIEW_R, 0, 1.0), ("neither", 0, 0, 1.0),
+            ("level-r", MP_IN_VIEW | MP_IN_VIEW_R, -1, 1.0), ("bad", MP_IN_VIEW | MP_IN_VIEW_R | MP_BAD, 0, 1.0),
+            ("far", MP_IN_VIEW | MP_IN_VIEW_R, 0, float(up(20.0))), ("near", MP_IN_VIEW | MP_IN_VIEW_R, 0, 20.0)]
+    for j, (what, fl, lr, depth) in enumerate(rows):
+        b = base_desc(380 + j)
+        x, y = site(j)
+        Lk, Rk = s.L(x, y, 0, flip(b, 5)), s.Rt(x, y, 0, b)
+        q = s.mp(b, (x, y), (x, y), lvl_r=lr, depth=depth, flags=fl)
+        T.append((what, q))
+        if what in ("in-view", "level-r", "near"):
+            exp[Lk] = q
+        if what in ("in-view-r", "near"):
+            exp[Rk] = q
+
+    def check(c, tr):
+        t = {w: tr["q"][q] for w, q in T}
+        assert t["in-view"]["R_skip"] == "not in view R" and t["in-view-r"]["L"] is None
+        assert t["neither"]["gate"] == "not in view" and t["bad"]["gate"] == "bad" and t["far"]["gate"] == "far"
+        assert t["level-r"]["R_skip"] == "level -1" and t["near"]["gate"] is None
+    return s.case("gates", "mbTrackInView / mbTrackInViewR, mnTrackScaleLevelR != -1, isBad, mTrackDepth > thFarPoints",
+                  exp, 5, check, "level-r-minus1-searched", (1, 3))
+
+
+def right_radius():
+    """th 3: a right key inside the th-scaled radius but outside the unscaled one is no candidate. view_cos_r: the
+    float 0.998 is above the double 0.998 the reference compares with (radius 2.5), one float below is not (4.0)."""
+    s = Scene2("local2", 3)
+    R = f32(f32(2.5) * SF[0])
+    exp, T = {}, []
+    b = base_desc(390)
+    x, y = site(0)
+    out = s.Rt(x + f32(1.5) * R, y, 0, b)
+    q = s.mp(b, None, (x, y))
+    T.append((q, out, R, False))
+    for j, (cr, RR) in enumerate(((f32(0.998), 2.5), (up(0.998), 2.5), (down(0.998), 4.0))):
+        b = base_desc(391 + j)
+        x, y = site(1 + j)
+        k = s.Rt(x + f32(3.0), y, 0, flip(b, 5))
+        q = s.mp(b, None, (x, y), cos_r=cr)
+        T.append((q, k, f32(RR), RR == 4.0))
+        if RR == 4.0:
+            exp[k] = q
+
+    def check(c, tr):
+        assert float(f32(0.998)) > 0.998 > float(down(0.998))
+        for q, k, RR, inn in T:
+            t = tr["q"][q]["R"]
+            assert t["R"] == RR and rules_of(t)[c.g(k)] == ("best" if inn else "box")
+    return s.case("right-radius", "the right radius is RadiusByViewingCos(mTrackViewCosR) * scale, never * th", exp, 1,
+                  check, ("right-radius-th", "right-cos-float"), (3,))
+
+
+def right_window_edge():
+    """|d| == R is out (strict <), the first float inside is in: the right grid, x and y, both signs."""
+    s = Scene2("local2", 3)
+    R = f32(f32(2.5) * SF[0])
+    exp, T = {}, []
+    for j, (ax, sg) in enumerate([(0, 1), (0, -1), (1, 1), (1, -1)]):
+        u, v = site(j)
+        b = base_desc(400 + j)
+        c = [u, v]
+        c[ax] = f32(c[ax] + sg * R)
+        assert abs(f32(c[ax] - (u, v)[ax])) == R
+        out = s.Rt(c[0], c[1], 0, b)
+        while not abs(f32(c[ax] - (u, v)[ax])) < R:
+            c[ax] = down(c[ax]) if sg > 0 else up(c[ax])
+        inn = s.Rt(c[0], c[1], 0, flip(b, 10))
+        q = s.mp(b, None, (u, v))
+        T.append((q, out, inn))
+        exp[inn] = q
+
+    def check(c, tr):
+        for q, out, inn in T:
+            r = rules_of(tr["q"][q]["R"])
+            assert r[c.g(out)] == "box" and r[c.g(inn)] == "best"
+    return s.case("right-window-edge", "box: |d| < r strict, in the right grid", exp, 4, check, "right-radius-th", (1, 3))
+
+
+def right_ties_ratio():
+    """The right camera's enumeration order and its ratio rule: three equal best distances around a corner of four
+    cells (column-major order wins; the runner-up is on another octave, so 20 against 20 is no ratio failure);
+    duplicates at 0 on one octave; (63, 90) at 0.7 on one octave, kept in float; (90, 91) across octaves, kept."""
+    s = Scene2("local2", 1, nnratio=0.7)
+    exp, T = {}, []
+    for j, dup in enumerate((False, True)):
+        b = base_desc(410 + j)
+        x0, y0 = f32(20.5 * 11.75 + 94 * j), f32(20.5 * 10.0)   # cell corners (20 | 21, 20 | 21) and (28 | 29, 20 | 21)
+        d = 0 if dup else 20
+        S = s.Rt(x0 + f32(1), y0 + f32(1), 1, flip(b, d))
+        Q = s.Rt(x0 + f32(1), y0 - f32(1), 1 if dup else 0, flip(b, d))
+        P = s.Rt(x0 - f32(1), y0 + f32(1), 1, flip(b, d))
+        q = s.mp(b, None, (x0, y0), lvl_r=1)
+        T.append((q, [P, Q, S], d, d))
+        exp[P] = q
+    for j, (d, d2, o2) in enumerate(((63, 90, 0), (90, 91, 1))):
+        b = base_desc(415 + j)
+        x, y = site(21 + j)
+        k1 = s.Rt(x, y, 1 if o2 else 0, flip(b, d))
+        k2 = s.Rt(x + f32(0.5), y, 0, flip(b, range(256 - d2, 256)))
+        q = s.mp(b, None, (x, y), lvl_r=o2)
+        T.append((q, [k1, k2], d, d2))
+        exp[k1] = q
+
+    def check(c, tr):
+        g = sd.PyGrid(c.F, 1)
+        P, Q, S = (c.g(h) for h in T[0][1])
+        assert (g.cell_of[P], g.cell_of[Q], g.cell_of[S]) == ((20, 21), (21, 20), (21, 21))
+        for q, ks, d, d2 in T:
+            t = tr["q"][q]["R"]
+            assert [i for i, _ in t["cands"]] == [c.g(h) for h in ks]
+            assert (t["best"], t["bd"], t["bd2"], t["outcome"]) == (c.g(ks[0]), d, d2, "kept")
+        assert tr["q"][T[0][0]]["R"]["bl"] != tr["q"][T[0][0]]["R"]["bl2"]
+        assert tr["q"][T[3][0]]["R"]["bl"] != tr["q"][T[3][0]]["R"]["bl2"] and sd.ratio_rejects(90, 91, 0.7)
+        assert not sd.ratio_rejects(63, 90, 0.7) and sd.ratio_rejects(63, 90, 0.7, double=True)
+    return s.case("right-ties-ratio", "right camera: strict < keeps the first enumerated; ratio in float, same octave only",
+                  exp, 4, check, ("right-ratio-cross-level", "right-ratio-double"), (1, 3))
+
+
+def list_depth(K):
+    """The K nearest candidates of a point are all taken (K earlier points with observations, one each), so its
+    (K + 1)-th wins; on both cameras. Neighbouring candidates are on alternating octaves (no ratio test)."""
+    s = Scene2("local2", 1)
+    b = base_desc(420)
+    x, y = site(8)
+    exp = {}
+    KL = [s.L(x + f32(0.125) * j, y, j % 2, flip(b, 2 * (j + 1))) for j in range(K + 2)]
+    KR = [s.Rt(x + f32(0.125) * j, y, j % 2, flip(b, 2 * (j + 1))) for j in range(K + 2)]
+    for j in range(K):
+        q = s.mp(flip(b, 2 * (j + 1)), (x, y), (x, y), lvl=1)
+        exp[KL[j]] = exp[KR[j]] = q
+    P = s.mp(b, (x, y), (x, y), lvl=1)
+    exp[KL[K]] = exp[KR[K]] = P
+
+    def check(c, tr):
+        for side, ks in (("L", KL), ("R", KR)):
+            t = tr["q"][P][side]
+            r = rules_of(t)
+            assert [r[c.g(h)] for h in ks] == ["blocked"] * K + ["best", "lost"]
+            assert (t["bd"], t["bd2"]) == (2 * (K + 1), 2 * (K + 2)) and t["bl"] != t["bl2"]
+        assert K >= 4   # k_sbp_block4 keeps 4 keys per search: the winner is beyond them
+    return s.case(f"list-depth-{K}", "blocked candidates are skipped however many: the (K + 1)-th nearest wins", exp,
+                  2 * (K + 1), check, "no-sequence", (1, 3))
+
+
+LADDER = 13
+
+
+def ladder(reverse):
+    """13 points, each depending on the one before through both cameras: point k's left best X[k] carries
+    l2r -> B[k]; its right candidates are B[k] (nearer) and C[k], and r2l[C[k]] = X[k + 1]. Point 0 takes X, writes
+    B as the partner, so its right search is pushed to C, whose partner write takes X[1]; point 1 therefore takes
+    its second left choice Y (no partner) and B[1] on the right, which writes nothing into X[2]; point 2 is point 0
+    again. Reversed, every point finds its X free and the r2l write of the next point in the list replaces it."""
+    s = Scene2("local2", 1)
+    X, Y, B, C, D = [], [], [], [], []
+    for k in range(LADDER):
+        b = base_desc(430 + k)
+        D.append(b)
+        x, y = site(k)
+        X.append(s.L(x, y, 0, flip(b, 10)))
+        Y.append(s.L(x + f32(0.5), y, 0, flip(b, range(200, 222))))
+        B.append(s.Rt(x, y, 0, flip(b, 5)))
+        C.append(s.Rt(x + f32(0.5), y, 0, flip(b, range(200, 215))))
+        s.link[X[k]] = B[k]
+        if k:
+            s.link[C[k - 1]] = X[k]
+    order = list(range(LADDER))[::-1] if reverse else list(range(LADDER))
+    Q = {}
+    for k in order:
+        x, y = site(k)
+        Q[k] = s.mp(D[k], (x, y), (x, y))
+    exp, n = {}, 0
+    for k in range(LADDER):
+        if reverse:
+            exp.update({X[k]: Q[k - 1] if k else Q[0], B[k]: Q[k], C[k]: Q[k]})
+            n += 4 if k < LADDER - 1 else 3
+        elif k % 2 == 0:
+            exp.update({X[k]: Q[k], B[k]: Q[k], C[k]: Q[k]})
+            if k + 1 < LADDER:
+                exp[X[k + 1]] = Q[k]
+            n += 4 if k + 1 < LADDER else 3
+        else:
+            exp.update({Y[k]: Q[k], B[k]: Q[k]})
+            n += 2
+
+    def check(c, tr):
+        for k in range(1, LADDER):
+            t = tr["q"][Q[k]]
+            if reverse:
+                assert t["L"]["best"] == c.g(X[k]) and t["R"]["best"] == c.g(C[k])
+                assert tr["q"][Q[k - 1]]["writes"][2][1:3] == [c.g(X[k]), QID + Q[k]]   # replaces point k
+            elif k % 2:
+                assert rules_of(t["L"])[c.g(X[k])] == "blocked" and t["L"]["best"] == c.g(Y[k])
+                assert t["R"]["best"] == c.g(B[k]) and c.mvp0[c.g(X[k])] == -1
+            else:
+                assert t["L"]["best"] == c.g(X[k]) and rules_of(t["R"])[c.g(B[k])] == "blocked"
+        assert LADDER - 1 >= 12
+    return s.case("ladder-reversed" if reverse else "ladder", "a chain of 12 dependencies alternating cameras through partner writes",
+                  exp, n, check, "partner-guarded" if reverse else "no-sequence", (1, 3))
+
+
+def cameras_apart():
+    """A left projection on a right keypoint's coordinates finds nothing, and the converse: each search walks its
+    own camera's grid only."""
+    s = Scene2("local2", 1)
+    b, b1 = base_desc(450), base_desc(451)
+    (x, y), (x1, y1) = site(0), site(1)
+    s.Rt(x, y, 0, b)
+    q0 = s.mp(b, (x, y), None)
+    s.L(x1, y1, 0, b1)
+    q1 = s.mp(b1, None, (x1, y1))
+
+    def check(c, tr):
+        assert tr["q"][q0]["L"]["cands"] == [] and tr["q"][q1]["R"]["cands"] == []
+    return s.case("cameras-apart", "mGrid holds left rows, mGridRight right rows", {}, 0, check, "one-grid", (1, 3))
+
+
+# ================================================================ last frame
+def lf_two_entries():
+    s = Scene2("lastframe2", TH_LF)
+    b = base_desc(500)
+    (x, y), (xr, yr) = site(0), site(9)
+    Lk, Rk = s.L(x, y, 0, flip(b, 5)), s.Rt(xr, yr, 0, flip(b, 3))
+    q = s.pt(b, (x, y), (xr, yr))
+
+    def check(c, tr):
+        t = tr["q"][q]
+        assert t["L"]["best"] == c.g(Lk) and t["R"]["best"] == c.g(Rk) and t["R"]["outcome"] == "kept"
+    return s.case("two-entries", "entry 2q the left best, 2q + 1 the right best; both count", {Lk: q, Rk: q}, 2, check,
+                  "right-left-grid")
+
+
+def lf_left_window():
+    """An empty left window skips the right search (its window holds a distance-0 key); a left window holding only
+    a blocked candidate, or only one beyond TH_HIGH, does not."""
+    s = Scene2("lastframe2", TH_LF)
+    exp, T = {}, []
+    for j, what in enumerate(("empty", "blocked", "far")):
+        b = base_desc(510 + j)
+        x, y = site(j)
+        if what == "blocked":
+            s.L(x, y, 0, flip(b, 5), held=(77, 3))
+        if what == "far":
+            s.L(x, y, 0, flip(b, 101))
+        Rk = s.Rt(x, y, 0, b)
+        q = s.pt(b, (x, y), (x, y))
+        T.append((what, q))
+        if what != "empty":
+            exp[Rk] = q
+
+    def check(c, tr):
+        t = {w: tr["q"][q] for w, q in T}
+        assert t["empty"]["L"]["outcome"] == "empty" and t["empty"]["R"] is None
+        assert t["blocked"]["L"]["outcome"] == "none" and t["blocked"]["R"]["outcome"] == "kept"
+        assert t["far"]["L"]["outcome"] == "distance" and t["far"]["R"]["outcome"] == "kept"
+    return s.case("left-window", "vIndices2.empty() alone `continue`s past the right search", exp, 2, check,
+                  ("empty-left-searches-right", "blocked-left-is-empty"))
+
+
+def lf_right_outside():
+    """The right projection is past the image on either side, negative, or in the last grid column: only the
+    window decides."""
+    s = Scene2("lastframe2", TH_LF)
+    exp, T = {}, []
+    spots = [((752.5, 150.0), (746.0, 150.0)), ((-3.0, 150.0), (2.0, 150.0)), ((300.0, -3.0), (300.0, 2.0)),
+             ((300.0, 480.5), (300.0, 474.0)), ((748.0, 300.0), (745.0, 300.0))]
+    for j, (ruv, kxy) in enumerate(spots):
+        b = base_desc(520 + j)
+        x, y = site(8 + j)
+        Lk = s.L(x, y, 0, flip(b, 5))
+        Rk = s.Rt(kxy[0], kxy[1], 0, flip(b, 3))
+        q = s.pt(b, (x, y), ruv)
+        T.append((q, Rk))
+        exp[Lk] = exp[Rk] = q
+
+    def check(c, tr):
+        g = sd.PyGrid(c.F, 1)
+        for q, Rk in T:
+            assert c.g(Rk) in g.cell_of and tr["q"][q]["R"]["best"] == c.g(Rk)
+        assert g.cell_of[c.g(T[4][1])][0] == 63 and g.cell_of[c.g(T[0][1])][0] == 63
+    return s.case("right-outside", "no bounds test on the right projection", exp, 10, check, "right-bounds")
+
+
+def lf_right_claims():
+    """A right key claimed by an earlier point's right entry blocks a later point; a later point's claim stays
+    invisible: the earlier point (0 observations) takes the key first and the later one replaces it."""
+    s = Scene2("lastframe2", TH_LF)
+    b = base_desc(530)
+    (x, y), (x1, y1), (xr, yr) = site(0), site(1), site(9)
+    L0, L1 = s.L(x, y, 0, flip(b, 5)), s.L(x1, y1, 0, flip(b, 6))
+    Rk, Rk2 = s.Rt(xr, yr, 0, flip(b, 3)), s.Rt(xr + f32(1), yr, 0, flip(b, 30))
+    q0 = s.pt(b, (x, y), (xr, yr))
+    q1 = s.pt(b, (x1, y1), (xr, yr))
+    b2 = base_desc(531)
+    (x2, y2), (x3, y3), (xs, ys) = site(2), site(3), site(11)
+    L2, L3 = s.L(x2, y2, 0, flip(b2, 5)), s.L(x3, y3, 0, flip(b2, 6))
+    Rm, Rm2 = s.Rt(xs, ys, 0, flip(b2, 3)), s.Rt(xs + f32(1), ys, 0, flip(b2, 30))
+    q2 = s.pt(b2, (x2, y2), (xs, ys), obs=0)
+    q3 = s.pt(b2, (x3, y3), (xs, ys))
+
+    def check(c, tr):
+        assert rules_of(tr["q"][q1]["R"])[c.g(Rk)] == "blocked" and tr["q"][q1]["R"]["best"] == c.g(Rk2)
+        assert tr["q"][q2]["R"]["best"] == c.g(Rm) and tr["q"][q3]["R"]["best"] == c.g(Rm) and c.expect[c.g(Rm2)] == -1
+    return s.case("right-claims", "the right entry 2q + 1 sees the writes of entries < 2q + 1 only",
+                  {L0: q0, L1: q1, Rk: q0, Rk2: q1, L2: q2, L3: q3, Rm: q3}, 8, check, "right-sees-later")
+
+
+def lf_ladder(obs):
+    """The 13-point ladder of the single-camera suite on both cameras at once: point j's nearest key on either
+    camera is taken by point j - 1 (12 dependencies per camera). obs 0: holders block nobody."""
+    s = Scene2("lastframe2", TH_LF, check_ori=True)
+    b = base_desc(540)
+    u, v = site(17)
+    blk = lambda j: range(16 * j, 16 * j + 16)   # noqa: E731
+    K = {sd_: [s.kp(sd_, u + f32(0.125) * (j % 4), v + f32(0.125) * (j // 4), 0, flip(b, blk(j))) for j in range(LADDER)]
+         for sd_ in "LR"}
+    Q = []
+    for j in range(LADDER):
+        bits = list(range(16 * j, 16 * j + 6))
+        if j:
+            bits += list(range(16 * (j - 1), 16 * (j - 1) + 12))
+        Q.append(s.pt(flip(b, bits), (u, v), (u, v), obs=obs))
+    exp = {}
+    for sd_ in "LR":
+        for j in range(LADDER):
+            if obs:
+                exp[K[sd_][j]] = Q[j]
+            elif j < LADDER - 1:
+                exp[K[sd_][j]] = Q[j + 1]
+
+    def check(c, tr):
+        for sd_ in "LR":
+            for j in range(1, LADDER):
+                t = tr["q"][Q[j]][sd_]
+                if obs:
+                    assert rules_of(t)[c.g(K[sd_][j - 1])] == "blocked" and (t["best"], t["bd"]) == (c.g(K[sd_][j]), 22)
+                else:
+                    assert (t["best"], t["bd"]) == (c.g(K[sd_][j - 1]), 10)
+        assert tr["bins"][0] == 2 * LADDER
+    return s.case(f"ladder-obs{obs}", "blocked: a held slot with Observations() > 0, on both cameras", exp, 2 * LADDER, check,
+                  "no-sequence" if obs else "right-left-grid")
+
+
+def lf_preheld():
+    """Slots held before the search: 0 observations free, > 0 blocked, on both cameras."""
+    s = Scene2("lastframe2", TH_LF)
+    b, b1 = base_desc(550), base_desc(551)
+    (x, y), (x1, y1) = site(0), site(1)
+    La = s.L(x, y, 0, flip(b, 5), held=(77, 0))
+    Ra = s.Rt(x, y, 0, flip(b, 5), held=(78, 3))
+    q0 = s.pt(b, (x, y), (x, y))
+    Lb = s.L(x1, y1, 0, flip(b1, 5), held=(79, 2))
+    Rb = s.Rt(x1, y1, 0, flip(b1, 5), held=(80, 0))
+    q1 = s.pt(b1, (x1, y1), (x1, y1))
+
+    def check(c, tr):
+        assert rules_of(tr["q"][q0]["L"])[c.g(La)] == "best" and rules_of(tr["q"][q0]["R"])[c.g(Ra)] == "blocked"
+        assert rules_of(tr["q"][q1]["L"])[c.g(Lb)] == "blocked" and rules_of(tr["q"][q1]["R"])[c.g(Rb)] == "best"
+    return s.case("preheld", "Observations() == 0 frees a held slot, > 0 blocks it", {La: q0, Rb: q1}, 2, check,
+                  "blocked-left-is-empty")
+
+
+def lf_no_uright_gate():
+    """A two-camera frame that carries mvuRight: a left key with uR > 0 far from u - mbf * invzc stays a candidate."""
+    s = Scene2("lastframe2", TH_LF, stereo=True)
+    b = base_desc(560)
+    x, y = site(0)
+    Lk = s.L(x, y, 0, flip(b, 5), ur=400.0)
+    q = s.pt(b, (x, y), site(30))
+
+    def check(c, tr):
+        assert abs(f32(sd.py_ur(x, MBF, 0.5) - f32(400.0))) > tr["q"][q]["L"]["R"] and c.F.uright[c.g(Lk)] > 0
+        assert rules_of(tr["q"][q]["L"])[c.g(Lk)] == "best"
+    return s.case("no-uright-gate", "the mvuRight test needs Nleft == -1", {Lk: q}, 1, check, "stereo-gate")
+
+
+def lf_level_range(o, fw, bw):
+    s = Scene2("lastframe2", TH_LF, fw=fw, bw=bw)
+    b = base_desc(570 + o)
+    lo, hi = (o, NLEVELS - 1) if fw else (0, o) if bw else (o - 1, o + 1)
+    u, v = site(17)
+    Lk = s.L(u, v, o, flip(b, 50))
+    kps = {}
+    for oc in range(NLEVELS):
+        kps[oc] = s.Rt(u + f32(0.25) * oc, v, oc, flip(b, (20 + oc) if lo <= oc <= hi else oc))
+    q = s.pt(b, (u, v), (u, v), octave=o)
+    best = min(oc for oc in kps if lo <= oc <= hi)
+
+    def check(c, tr):
+        r = rules_of(tr["q"][q]["R"])
+        for oc, h in kps.items():
+            assert (r[c.g(h)] == "level") == (not lo <= oc <= hi), (oc, r[c.g(h)])
+        assert r[c.g(kps[best])] == "best"
+    mode = "fw" if fw else "bw" if bw else "std"
+    return s.case(f"level-range-L{o}-{mode}", f"level range [{lo}, {hi}] in the right grid", {Lk: q, kps[best]: q}, 2, check,
+                  "right-left-grid")
+
+
+def lf_gates():
+    """invalid, invzc < 0, u or v one float outside the bounds: neither camera is searched. u exactly on the bound
+    is searched."""
+    s = Scene2("lastframe2", TH_LF)
+    exp, T = {}, []
+    rows = [("invalid", (300.0, 100.0), 0.5, 0), ("invzc", (300.0, 200.0), -0.5, 1),
+            ("bounds", (float(up(752.0)), 300.0), 0.5, 1), ("bounds", (float(down(0.0)), 100.0), 0.5, 1),
+            ("bounds", (500.0, float(up(480.0))), 0.5, 1), ("bounds", (600.0, float(down(0.0))), 0.5, 1),
+            (None, (752.0, 400.0), 0.5, 1)]
+    for j, (gate, (u, v), iz, valid) in enumerate(rows):
+        b = base_desc(580 + j)
+        kx, ky = min(max(u, 3.0), 746.0), min(max(v, 3.0), 474.0)
+        Lk = s.L(kx, ky, 0, flip(b, 5))
+        Rk = s.Rt(*site(7 * (j % 5) + j // 5 + 2), 0, b)
+        q = s.pt(b, (u, v), (s.k["R"][Rk[1]][0], s.k["R"][Rk[1]][1]), invzc=iz, valid=valid)
+        T.append((q, gate))
+        if gate is None:
+            exp[Lk] = exp[Rk] = q
+
+    def check(c, tr):
+        for q, gate in T:
+            assert tr["q"][q]["gate"] == gate and (tr["q"][q]["L"] is None) == (gate is not None)
+    return s.case("gates", "valid, invzc < 0, u / v against the image bounds: the whole point is skipped", exp, 2, check,
+                  "gates-left-only")
+
+
+def _rsite(j):
+    return f32(20.0 + 24 * (j % 30)), f32(20.0 + 40 * (j // 30))
+
+
+def lf_rotation(pname, check_ori):
+    """The bin plans of sbp_patterns with the votes split between the cameras: entry j votes through its left
+    match (j even; its right window is empty) or through its right match (j odd; its left window holds one key
+    beyond TH_HIGH, so the right search runs and the left casts no vote)."""
+    s = Scene2("lastframe2", 1, check_ori=check_ori)
+    plan = PLANS[pname]
+    void = (f32(740.0), f32(470.0))
+    T = []
+    for j, (aq, ak, bn) in enumerate(plan):
+        b = base_desc(200 + j)
+        u, v = _rsite(j)
+        if j % 2 == 0:
+            k = s.L(u, v, 0, flip(b, 3), angle=ak)
+            q = s.pt(b, (u, v), void, angle=aq)
+        else:
+            s.L(u, v, 0, flip(b, 120))
+            k = s.Rt(u, v, 0, flip(b, 3), angle=ak)
+            q = s.pt(b, (u, v), (u, v), angle=aq)
+        T.append((q, k, bn))
+    bins = _plan_bins(plan)
+    keep = sd.py_three_maxima(bins)
+    exp = {k: q for q, k, bn in T if (not check_ori) or bn in keep}
+    # hist-left-only answers differently where a dropped bin holds a right vote or the left votes keep other bins
+    lbins = _plan_bins(plan[0::2])
+    lkeep = sd.py_three_maxima(lbins)
+    differs = check_ori and any((bn in keep) != (bn in lkeep) if j % 2 == 0 else bn not in keep for j, (_, _, bn) in enumerate(plan))
+
+    def check(c, tr):
+        assert (tr["bins"], tr["kept_bins"]) == ((bins, keep) if check_ori else (None, None))
+        for q, k, bn in T:
+            side = "L" if k[0] == "L" else "R"
+            assert tr["q"][q][side]["outcome"] == ("kept" if k in exp else "dropped bin")
+        if check_ori:
+            assert any(k[0] == "R" and k not in exp for _, k, _ in T) == any(bn not in keep for _, _, bn in plan[1::2])
+    return s.case(f"rot-{pname}-ori{int(check_ori)}", "rotation histogram over both cameras' matches", exp, len(exp), check,
+                  ("right-left-grid", "hist-left-only") if differs else ("right-left-grid",))
+
+
+# ================================================================ padding
+def _clone(case, **kw):
+    c = Case2(**case.__dict__)
+    c.__dict__.update(kw)
+    return c
+
+
+def _positions(case):
+    if case.kind == "local2":
+        return list(zip(case.q["proj_x"], case.q["proj_y"])) + list(zip(case.q["proj_xr"], case.q["proj_yr"]))
+    return list(zip(case.q["u"], case.q["v"])) + [tuple(r) for r in case.ruv]
+
+
+def pad_keys(case, n=PAD_N):
+    """Inert right-camera keypoints up to n rows, after every planted row (nleft and every planted index stay):
+    half where PosInGrid is false, half in the image corner farthest from every projection of either camera, more
+    than the largest radius of any level away from all of them, so no window at any level range enumerates them."""
+    F = case.F
+    add = n - F.N
+    rng = np.random.default_rng(5)
+    k = np.zeros(add, KEYPOINT_DTYPE)
+    x0, x1, y0, y1 = F.bounds
+    corners = [(x0 + 3, y0 + 3), (x1 - 14, y0 + 3), (x0 + 3, y1 - 12), (x1 - 14, y1 - 12)]
+    pos = _positions(case)
+    cx, cy = max(corners, key=lambda c: min(max(abs(c[0] - a), abs(c[1] - b)) for a, b in pos))
+    Rmax = float(f32(f32(max(10.0, case.par["th"] * 4.0)) * SF[NLEVELS - 1]))
+    if case.kind == "lastframe2":
+        Rmax = float(f32(f32(case.par["th"]) * SF[NLEVELS - 1]))
+    lv = case.q["scale_level" if case.kind == "local2" else "octave"]
+    Rmax = min(Rmax, max(float(f32(f32(max(10.0, case.par["th"] * 4.0)) * SF[int(v)])) for v in lv))
+    assert all(max(abs(cx - a), abs(cy - b)) > Rmax + 8 for a, b in pos), case.name
+    half = add // 2
+    k["x"][:half] = x1 + 40 + rng.uniform(0, 50, half)
+    k["y"][:half] = rng.uniform(y0, y1, half)
+    k["x"][half:] = cx + rng.uniform(0, 5, add - half)
+    k["y"][half:] = cy + rng.uniform(0, 5, add - half)
+    k["octave"] = rng.integers(0, NLEVELS, add)
+    k["size"], k["response"], k["class_id"] = 31.0, 20.0, -1
+    desc = rng.integers(0, 256, (add, 32), dtype=np.uint8)
+    ur = None if F.uright is None else np.concatenate([F.uright, np.full(add, -1, np.float32)])
+    F2 = MatchFrame(np.concatenate([F.keys, k]), np.concatenate([F.desc, desc]), F.bounds, SF, ur, MBF, nleft=F.nleft,
+                    l2r=F.l2r, r2l=np.concatenate([F.r2l, np.full(add, -1, np.int32)]))
+    return _clone(case, name=case.name + "+keys", F=F2, mvp0=np.concatenate([case.mvp0, np.full(add, -1, np.int32)]),
+                  obs=np.concatenate([case.obs, np.zeros(add, np.int32)]),
+                  expect=np.concatenate([case.expect, np.full(add, -1, np.int32)]))
+
+
+def pad_queries(case, n=PAD_N):
+    """Inert points up to n (flags 0 / valid 0, every other field as a live record's)."""
+    add = n - len(case.q)
+    rng = np.random.default_rng(6)
+    q = np.zeros(add, case.q.dtype)
+    x0, x1, y0, y1 = case.F.bounds
+    ruv = case.ruv
+    if case.kind == "local2":
+        q["proj_x"], q["proj_xr"] = rng.uniform(x0, x1, add), rng.uniform(x0, x1, add)
+        q["proj_y"], q["proj_yr"] = rng.uniform(y0, y1, add), rng.uniform(y0, y1, add)
+        q["scale_level"] = q["scale_level_r"] = rng.integers(0, NLEVELS, add)
+        q["view_cos"] = q["view_cos_r"] = 0.999
+        q["depth"] = 1.0
+    else:
+        q["u"], q["v"], q["invzc"] = rng.uniform(x0, x1, add), rng.uniform(y0, y1, add), 0.5
+        q["octave"] = rng.integers(0, NLEVELS, add)
+        ruv = np.concatenate([ruv, np.stack([rng.uniform(x0, x1, add), rng.uniform(y0, y1, add)], 1).astype(np.float32)])
+    q["observations"], q["id"] = 1, 9000 + np.arange(add)
+    q["desc"] = rng.integers(0, 256, (add, 32), dtype=np.uint8)
+    return _clone(case, name=case.name + "+queries", q=np.concatenate([case.q, q]), ruv=ruv)
+
+
+def with_th(case, th):
+    assert th in case.ths
+    par = dict(case.par)
+    par["th"] = th
+    return _clone(case, name=f"{case.name}@th{th}", par=par)
+
+
+# ================================================================ the list
+LF_PLANS = ("ties", "tenth-10", "tenth-30", "tenth-60", "half-way", "one-bin", "two-bins")
+
+
+def _build():
+    out = [four_writes(), link_guards(), partner_overwrites(), last_writer(2), last_writer(6), last_writer(7),
+           own_partner_seen(), left_ratio_cancels(), left_far_right_runs(), gates(), right_radius(), right_window_edge(),
+           right_ties_ratio(), list_depth(4), list_depth(5), ladder(False), ladder(True), cameras_apart()]
+    out += [lf_two_entries(), lf_left_window(), lf_right_outside(), lf_right_claims(), lf_ladder(1), lf_ladder(0),
+            lf_preheld(), lf_no_uright_gate(), lf_gates()]
+    for o in (0, NLEVELS - 1):
+        out += [lf_level_range(o, False, False), lf_level_range(o, True, False), lf_level_range(o, False, True)]
+    for p in LF_PLANS:
+        out += [lf_rotation(p, True), lf_rotation(p, False)]
+    assert len({c.name for c in out}) == len(out)
+    return out
+
+
+_CASES = None
+
+
+def all_cases():
+    global _CASES
+    if _CASES is None:
+        _CASES = _build()
+    return _CASES
+
+
+SEVEN_WRITERS = "last-writer-7-local2"
+
+
+# ================================================================ running a case
+def run_definition(case, variant=None):
+    """-> (nmatches, trace, slots) by oracle/sbp_definition.py, tracing on."""
+    mvp, p = case.mvp0.copy(), case.par
+    if case.kind == "local2":
+        n, tr = sd.py_sbp_local_two(case.F, mvp, case.obs, case.q, p["th"], p["nnratio"], p["bfar"], p["thfar"],
+                                    trace=True, variant=variant)
+    else:
+        n, tr = sd.py_sbp_lastframe_two(case.F, mvp, case.obs, case.q, case.ruv, p["th"], p["fw"], p["bw"],
+                                        p["check_ori"], trace=True, variant=variant)
+    return n, tr, mvp
+
+
+def run_oracle(oracle_lib, case):
+    """-> (nmatches, slots) by the C++ oracle's two-camera entries."""
+    mvp, p = case.mvp0.copy(), case.par
+    om = oracle_lib.OracleMatcher(p["nnratio"], p["check_ori"])
+    if case.kind == "local2":
+        n = om.sbp_local(case.F, mvp, case.obs, case.q, p["th"], p["bfar"], p["thfar"])
+    else:
+        n = om.sbp_lastframe_stereo(case.F, mvp, case.obs, case.q, case.ruv, p["th"], p["fw"], p["bw"])
+    return n, mvp

@@ -19,8 +19,8 @@ is asserted as well: k_sbp_proj reports {0, 0, passes}, the one-workgroup and mu
 the pass forms pairs <= candidates. The bin plans also run through SearchForInitialization, whose
 k_init_commit is the third copy of the histogram code.
 
-Out of scope: the two-camera forms (k_sbp_block2, k_sbp_block4, k_sbp_local2, k_sbp_proj2). SearchByBoW has
-its own planted cases (tests/test_gpu_sbow_adversarial.py).
+The two-camera forms (k_sbp_block2, k_sbp_block4, k_sbp_local2, k_sbp_proj2) have their own planted cases in
+tests/test_gpu_sbp_two_adversarial.py, SearchByBoW in tests/test_gpu_sbow_adversarial.py.
 """
 import ctypes
 

@@ -3,15 +3,16 @@ SearchByProjection (local map, ORBmatcher.cc:43-213; last frame, :1676-1887) and
 (:223-425): hand-built known-answer cases for each quirk of the reference (the left ratio-test
 `continue` that also skips the right search, the right radius not scaled by th, the right BoW ratio
 test disabled by "|| true", the empty left window skipping the right last-frame search, the stereo
-partner writes through mvLeftToRightMatch / mvRightToLeftMatch), and a pure-Python literal
-restatement of the local-map branch compared with the C oracle on seeded cases. No GPU needed."""
+partner writes through mvLeftToRightMatch / mvRightToLeftMatch), and the literal Python restatement of
+the local-map branch (oracle/sbp_definition.py, py_sbp_local_two) compared with the C oracle on seeded
+cases. No GPU needed."""
 import numpy as np
 import pytest
 
+from oracle.sbp_definition import py_sbp_local_two
 from orb_slam3_ros_amd import synth_match as sm
 from orb_slam3_ros_amd.extractor import KEYPOINT_DTYPE
 from orb_slam3_ros_amd.matcher import MAP_POINT_DTYPE, PROJ_POINT_DTYPE, FeatureVector, MatchFrame
-from test_oracle_matcher import PyGrid, _ham, f32
 
 W = H = 512
 
@@ -142,67 +143,6 @@ def test_bow_right_ratio_disabled(O):
     ff2 = FeatureVector({5: [0, 1, 2]})
     n, out = O.OracleMatcher(0.6, False).search_by_bow(kk, D[None], np.array([42], np.int32), fk, F2, ff2)
     assert n == 0 and (out == -1).all()
-
-
-def py_sbp_local_two(F, mvp, obs, mps, th, nnratio):
-    """ORBmatcher.cc:43-213 with Nleft != -1, literal; rows in the global numbering."""
-    nl = F.nleft
-    gl = PyGrid(MatchFrame(F.keys[:nl], F.desc[:nl], F.bounds, F.scale_factors))
-    gr = PyGrid(MatchFrame(F.keys[nl:], F.desc[nl:], F.bounds, F.scale_factors))
-    obs = obs.copy()
-    n = 0
-
-    def best2(cands, off):
-        bd, bl, bd2, bl2, bi = 256, -1, 256, -1, -1
-        for c in cands:
-            idx = c + off
-            if mvp[idx] >= 0 and obs[idx] > 0:
-                continue
-            d = _ham(mp["desc"], F.desc[idx])
-            if d < bd:
-                bd2, bd, bl2, bl, bi = bd, d, bl, int(F.keys[idx]["octave"]), idx
-            elif d < bd2:
-                bl2, bd2 = int(F.keys[idx]["octave"]), d
-        return bd, bl, bd2, bl2, bi
-
-    for mp in mps:
-        inv, invr = bool(mp["flags"] & sm.MP_IN_VIEW), bool(mp["flags"] & sm.MP_IN_VIEW_R)
-        if (not inv and not invr) or (mp["flags"] & sm.MP_BAD):
-            continue
-        if inv:
-            lvl = int(mp["scale_level"])
-            r = f32(2.5) if float(mp["view_cos"]) > 0.998 else f32(4.0)
-            if th != 1.0:
-                r = f32(r * f32(th))
-            R = f32(r * F.scale_factors[lvl])
-            cands = gl.area(mp["proj_x"], mp["proj_y"], R, lvl - 1, lvl)
-            if cands:
-                bd, bl, bd2, bl2, bi = best2(cands, 0)
-                if bd <= 100:
-                    if bl == bl2 and bd > f32(nnratio) * f32(bd2):
-                        continue
-                    mvp[bi], obs[bi] = mp["id"], mp["observations"]
-                    if F.l2r[bi] != -1:
-                        mvp[F.l2r[bi] + nl], obs[F.l2r[bi] + nl] = mp["id"], mp["observations"]
-                        n += 1
-                    n += 1
-        if invr and int(mp["scale_level_r"]) != -1:
-            lvl = int(mp["scale_level_r"])
-            r = f32(2.5) if float(mp["view_cos_r"]) > 0.998 else f32(4.0)
-            R = f32(r * F.scale_factors[lvl])
-            cands = gr.area(mp["proj_xr"], mp["proj_yr"], R, lvl - 1, lvl)
-            if not cands:
-                continue
-            bd, bl, bd2, bl2, bi = best2(cands, nl)
-            if bd <= 100:
-                if bl == bl2 and bd > f32(nnratio) * f32(bd2):
-                    continue
-                if F.r2l[bi - nl] != -1:
-                    mvp[F.r2l[bi - nl]], obs[F.r2l[bi - nl]] = mp["id"], mp["observations"]
-                    n += 1
-                mvp[bi], obs[bi] = mp["id"], mp["observations"]
-                n += 1
-    return n
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
