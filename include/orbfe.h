@@ -768,6 +768,57 @@ int orbfe_search_by_projection_lastframe_slabs(const orbfe_keypoint* d_kps, cons
                                                int32_t nframes, int32_t checkOri, int32_t* mvp_out, int32_t* nmatches,
                                                int32_t* n_keys, void* stream);
 
+/* TrackLocalMap's SearchLocalPoints (Tracking.cc:3382-3452: Frame::isInFrustum + MapPoint::PredictScale over the
+ * local map points, then ORBmatcher(nnratio).SearchByProjection(F, mvpLocalMapPoints, th, bFarPoints,
+ * thFarPoints)) for the frames of a batch extraction, in one call and one kernel launch, one workgroup per
+ * frame, on the same slabs as orbfe_search_by_projection_lastframe_slabs. Single-camera frames only.
+ * One frame of the batch: */
+typedef struct orbfe_local_job {
+    orbfe_camera cam;                 /* this frame's pose, Ow, fx..cy, mfLogScaleFactor, cos limit */
+    const orbfe_map_point_3d* pts;    /* host, mvpLocalMapPoints order; NULL when n_pts == 0 */
+    int32_t n_pts;                    /* 0: frame skipped */
+    const int32_t* skip;              /* host indices into pts that get ORBFE_MP_SKIP for THIS frame only
+                                         (the frame's own matched points, Tracking.cc:3386-3405); may be NULL */
+    int32_t n_skip;
+    float th;
+    uint8_t* in_view;                 /* host [n_pts] or NULL: 1 where isInFrustum passed (IncreaseVisible) */
+} orbfe_local_job;                    /* 128 bytes */
+
+/* A job takes at most this many points (of which at most 2,048 may pass isInFrustum). */
+#define ORBFE_LOCAL_BATCH_MAX_POINTS 65536
+
+/* d_kps / d_desc / d_counts / cap / base / step / d_uright / geom / stream: exactly as
+ * orbfe_search_by_projection_lastframe_slabs (frame f is image base + f*step, its N is read on the device,
+ * geom->two_cams must be 0). model: the frames' mpCamera (pinhole or a single KannalaBrandt8 camera), or NULL
+ * for the pinhole camera of each job's cam. mvp_in / mvp_obs (host [nframes][cap]): every frame's
+ * mvpMapPoints handles and their Observations() before the search; slots [N, cap) are not read.
+ * Row f of mvp_out (host [nframes][cap]), nmatches[f] and n_to_match[f] are bit-identical to
+ * orbfe_search_local_points (with a KannalaBrandt8 model: orbfe_search_local_points_rig with rig->left =
+ * *model) on the host copy of frame f with job f's points, ORBFE_MP_SKIP OR-ed in at the job's skip indices,
+ * row f of mvp_in / mvp_obs, the job's cam and th and the call's bFarPoints, thFarPoints and nnratio; slots
+ * [N, cap) of the row are -1; n_keys[f] = N. n_to_match counts the points in view before the far / level
+ * gates, and job f's in_view marks them. Rows never affect each other. Jobs with the same pts pointer and
+ * n_pts share one upload (512 frames can project one local map; skip is what differs per frame).
+ * A job with n_pts == 0: nmatches[f] = n_to_match[f] = 0 and the row is mvp_in's. A frame with N == 0 matches
+ * nothing, but isInFrustum still runs over its points as in the reference (n_to_match and in_view are
+ * reported, as orbfe_search_local_points does). A frame whose N exceeds min(cap, 2048), or with more than
+ * 2,048 points in view, cannot be refused on the host: nmatches[f] = ORBFE_E_CAPACITY, its row is mvp_in's
+ * row (slots beyond min(N, cap) -1), n_to_match and in_view are still reported, and every other frame is
+ * unaffected. The results are complete on return. nframes == 0 returns ORBFE_OK.
+ * ORBFE_E_ARG: nframes < 0, a NULL d_kps / d_desc / d_counts / geom / jobs / mvp_in / mvp_obs / mvp_out /
+ * nmatches / n_to_match / n_keys, cap <= 0, a negative base, step, n_pts or n_skip, NULL pts with n_pts > 0,
+ * NULL skip with n_skip > 0, a skip index outside [0, n_pts), geom->two_cams, geom without levels or scale
+ * factors, a bad model type. ORBFE_E_CAPACITY: an n_pts above ORBFE_LOCAL_BATCH_MAX_POINTS, or bounds that do
+ * not fit the one-workgroup index. Every refusal comes before any device work and before any write to an
+ * output. */
+int orbfe_search_local_points_slabs(const orbfe_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_counts,
+                                    int32_t cap, int32_t base, int32_t step, const float* d_uright,
+                                    const orbfe_frame* geom, const orbfe_camera_model* model,
+                                    const orbfe_local_job* jobs, int32_t nframes, const int32_t* mvp_in,
+                                    const int32_t* mvp_obs, int32_t bFarPoints, float thFarPoints, float nnratio,
+                                    int32_t* mvp_out, int32_t* nmatches, int32_t* n_to_match, int32_t* n_keys,
+                                    void* stream);
+
 /* The matching half of Fuse (ORBmatcher.cc:1148-1337 with sim3 = 0; :1339-1455, Fuse(pKF, Scw, ...)
  * with sim3 = 1; pinhole, bRight = false): for every point with id >= 0 not flagged BAD / SKIP (SKIP =
  * IsInKeyFrame(pKF), resp. already in pKF->GetMapPoints()), project, check and search the keyframe
@@ -1073,6 +1124,12 @@ int orbfe_matcher_last_bow_kf_batch(int32_t* out);
  * k_sbp_track_batch's one workgroup, out[1] skipped (n_pts == 0 or no keypoints), out[2] over the
  * workgroup's capacity (nmatches[f] = ORBFE_E_CAPACITY). All zero after a refused or empty call. */
 int orbfe_matcher_last_track_batch(int32_t* out);
+/* Of this thread's last orbfe_search_local_points_slabs: out[0] frames searched in k_local_batch's one
+ * workgroup, out[1] skipped (n_pts == 0, no keypoints or no point in view), out[2] over the workgroup's
+ * capacity (nmatches[f] = ORBFE_E_CAPACITY). All zero after a refused or empty call. */
+int orbfe_matcher_last_local_batch(int32_t* out);
+/* The number of distinct point arrays that call uploaded (jobs sharing pts and n_pts count once). */
+int orbfe_matcher_last_local_uploads(void);
 /* The number of k_kf_search passes of this thread's last orbfe_search_by_projection_sim3(_rig): the
  * reference's sequential "keypoint already matched" dependency needs one pass per link of a chain of
  * queries that each lose their best keypoint to the query before. The driver runs the passes in pairs and

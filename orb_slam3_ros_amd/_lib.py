@@ -170,6 +170,10 @@ _SIGS = {
     "orbfe_search_by_projection_lastframe_slabs": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp,
                                                             _c_int, _c_int, _vp, _vp, _vp, _vp]),
     "orbfe_matcher_last_track_batch": (_c_int, [_vp]),
+    "orbfe_search_local_points_slabs": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int,
+                                                 _vp, _vp, _c_int, _c_float, _c_float, _vp, _vp, _vp, _vp, _vp]),
+    "orbfe_matcher_last_local_batch": (_c_int, [_vp]),
+    "orbfe_matcher_last_local_uploads": (_c_int, []),
 }
 
 _lib = None

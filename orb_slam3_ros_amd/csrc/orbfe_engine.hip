@@ -1547,3 +1547,6 @@ int orbfe_descriptor_distance(const uint8_t* a, const uint8_t* b) {
 
 // Batched motion-model SearchByProjection(CurrentFrame, LastFrame) over the frames of a batch extraction.
 #include "orbfe_track_batch.hip"
+
+// Batched Tracking::SearchLocalPoints (isInFrustum + SearchByProjection(F, local map)) over the same frames.
+#include "orbfe_local_batch.hip"

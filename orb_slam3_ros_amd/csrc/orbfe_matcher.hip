@@ -2439,13 +2439,8 @@ __device__ __forceinline__ FrustumView mt_frustum_view(const CamDev& c, const fl
     o.stage = 3;
     return o;
 }
-__global__ __launch_bounds__(MT_NT) void k_frustum(CamDev c, const orbfe_map_point_3d* pts, int n,
-                                                   orbfe_map_point* track, int* n_to_match,
-                                                   orbfe_map_point* track_host = nullptr) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const orbfe_map_point_3d p = pts[i];
-    orbfe_map_point t;
+// A point's record before any view is checked (k_frustum, k_local_batch)
+__device__ __forceinline__ void mt_track_init(const orbfe_map_point_3d& p, orbfe_map_point& t) {
     // mTrackDepth is only written by a passing left view: otherwise the previous value stays
     t.proj_x = -1.f; t.proj_y = -1.f; t.proj_xr = 0.f; t.view_cos = 0.f; t.depth = p.track_depth;
     t.scale_level = 0;
@@ -2456,6 +2451,31 @@ __global__ __launch_bounds__(MT_NT) void k_frustum(CamDev c, const orbfe_map_poi
     t.view_cos_r = 0.f;
     t.scale_level_r = -1;
     memcpy(t.desc, p.desc, 32);
+}
+// isInFrustum's Nleft == -1 branch (Frame.cc:512-570) on an initialised record; true: the point is in view
+__device__ __forceinline__ bool mt_frustum_single(const CamDev& c, const orbfe_map_point_3d& p, orbfe_map_point& t) {
+    if (p.flags & (ORBFE_MP_SKIP | ORBFE_MP_BAD)) return false;
+    const FrustumView L = mt_frustum_view(c, c.R, c.t, c.Ow, c.cl, p);
+    if (L.stage >= 2) {   // mTrackProjX / Y are written once the projection is in the image
+        t.proj_x = L.u;
+        t.proj_y = L.v;
+    }
+    if (L.stage != 3) return false;
+    t.flags |= ORBFE_MP_IN_VIEW;
+    t.proj_xr = L.u - c.mbf * L.invz;
+    t.depth = L.depth;
+    t.scale_level = L.level;
+    t.view_cos = L.view_cos;
+    return true;
+}
+__global__ __launch_bounds__(MT_NT) void k_frustum(CamDev c, const orbfe_map_point_3d* pts, int n,
+                                                   orbfe_map_point* track, int* n_to_match,
+                                                   orbfe_map_point* track_host = nullptr) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const orbfe_map_point_3d p = pts[i];
+    orbfe_map_point t;
+    mt_track_init(p, t);
     bool in = false;
     if (c.two) {
         // Nleft != -1 (Frame.cc:575-586): both views checked, levels reset to -1, a view's fields
@@ -2483,20 +2503,8 @@ __global__ __launch_bounds__(MT_NT) void k_frustum(CamDev c, const orbfe_map_poi
             }
             in = L.stage == 3 || Rv.stage == 3;
         }
-    } else if (!(p.flags & (ORBFE_MP_SKIP | ORBFE_MP_BAD))) {
-        const FrustumView L = mt_frustum_view(c, c.R, c.t, c.Ow, c.cl, p);
-        if (L.stage >= 2) {   // mTrackProjX / Y are written once the projection is in the image
-            t.proj_x = L.u;
-            t.proj_y = L.v;
-        }
-        if (L.stage == 3) {
-            t.flags |= ORBFE_MP_IN_VIEW;
-            t.proj_xr = L.u - c.mbf * L.invz;
-            t.depth = L.depth;
-            t.scale_level = L.level;
-            t.view_cos = L.view_cos;
-            in = true;
-        }
+    } else {
+        in = mt_frustum_single(c, p, t);
     }
     track[i] = t;
     // the caller's copy of the records (orbfe_search_local_points_track): vector stores into mapped,

@@ -220,6 +220,23 @@ class StereoFrontEnd:
             self.kps, self.desc, self.counts, self.cap, 0, 2, self.uright if self.stereo == "rectified" else None,
             geom, cam, jobs, stream=stream)
 
+    def track_local_map(self, jobs, geom, mvp, mvp_obs, bFarPoints: bool = False, thFarPoints: float = 50.0,
+                        model=None, nnratio: float = 0.8, stream=None):
+        """TrackLocalMap's SearchLocalPoints (isInFrustum over each frame's local map points, then
+        SearchByProjection(F, mvpLocalMapPoints, th, bFarPoints, thFarPoints)) for all F frames of the last
+        run() in one launch, on the slabs track_motion_model reads. jobs: F matcher.LocalMapJob (pose, local
+        map points, th, skip indices); mvp / mvp_obs: int32 [F, cap] host arrays, the frames' mvpMapPoints
+        after pose optimisation and their Observations(). geom, stream: as track_motion_model.
+        -> (nmatches [F], n_to_match [F], n_keys [F], mvp_out [F, cap]), see ORBmatcher.SearchLocalPointsBatch."""
+        from .matcher import ORBmatcher
+        if self.stereo == "fisheye":
+            raise _lib.OrbfeError("track_local_map searches single-camera frames (stereo 'rectified' or 'none')")
+        if len(jobs) != self.F:
+            raise ValueError(f"one job per frame: {self.F}")
+        return ORBmatcher(nnratio).SearchLocalPointsBatch(
+            self.kps, self.desc, self.counts, self.cap, 0, 2, self.uright if self.stereo == "rectified" else None,
+            geom, jobs, mvp, mvp_obs, bFarPoints, thFarPoints, model=model, stream=stream)
+
     def host_frame(self, f: int):
         """(kps_left structured, desc_left, uright, depth) of frame f, copied to the host."""
         _, kp, d = self.host_image(2 * f)
@@ -291,6 +308,19 @@ class RGBDFrontEnd:
         """Frame::ComputeBoW for all F images of the last run(), on the caller's current torch stream
         (run()'s) or on `stream`. No host wait. -> vocabulary.BowBatch, allocated once and reused."""
         return _compute_bow(self, voc, levelsup, stream)
+
+    def track_local_map(self, jobs, geom, mvp, mvp_obs, bFarPoints: bool = False, thFarPoints: float = 50.0,
+                        nnratio: float = 0.8, stream=None):
+        """StereoFrontEnd.track_local_map for the F RGB-D frames of the last run(): the search reads the
+        undistorted keypoints (keys_un = mvKeysUn) and the mvuRight rows made from depth. Runs after the
+        caller's current torch stream (run()'s) or `stream`.
+        -> (nmatches [F], n_to_match [F], n_keys [F], mvp_out [F, cap])."""
+        from .matcher import ORBmatcher
+        if len(jobs) != self.F:
+            raise ValueError(f"one job per frame: {self.F}")
+        return ORBmatcher(nnratio).SearchLocalPointsBatch(
+            self.keys_un, self.desc, self.counts, self.cap, 0, 1, self.uright, geom, jobs, mvp, mvp_obs, bFarPoints,
+            thFarPoints, stream=stream)
 
     def host_frame(self, f: int):
         """(mvKeys, mvKeysUn, mDescriptors, mvuRight, mvDepth) of frame f, copied to the host."""

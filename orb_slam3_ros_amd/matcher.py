@@ -229,6 +229,33 @@ class TrackJob(ctypes.Structure):
         return j
 
 
+class LocalMapJob(ctypes.Structure):
+    """struct orbfe_local_job: one frame of ORBmatcher.SearchLocalPointsBatch (128 bytes)."""
+    _fields_ = [("cam", Camera), ("pts", ctypes.c_void_p), ("n_pts", ctypes.c_int32), ("skip", ctypes.c_void_p),
+                ("n_skip", ctypes.c_int32), ("th", ctypes.c_float), ("in_view", ctypes.c_void_p)]
+
+    @staticmethod
+    def make(cam: Camera, points, th: float, skip=None, want_in_view: bool = False):
+        """points: MAP_POINT_3D records in mvpLocalMapPoints order, or None / empty: the frame is skipped.
+        Jobs made from the same array share one upload. skip: indices into points that this frame does
+        not project (its own matched points). want_in_view: job.in_view_flags (uint8 [n_pts]) receives
+        mbTrackInView per point. The job keeps its arrays alive."""
+        j = LocalMapJob()
+        j.cam = cam
+        pts = None if points is None else _records(points, MAP_POINT_3D_DTYPE, "points")
+        j._points = pts
+        j.n_pts = 0 if pts is None else len(pts)
+        j.pts = pts.ctypes.data if j.n_pts else None
+        sk = None if skip is None else np.ascontiguousarray(skip, np.int32).reshape(-1)
+        j._skip = sk
+        j.n_skip = 0 if sk is None else len(sk)
+        j.skip = sk.ctypes.data if j.n_skip else None
+        j.th = float(th)
+        j.in_view_flags = np.zeros(j.n_pts, np.uint8) if want_in_view else None
+        j.in_view = j.in_view_flags.ctypes.data if want_in_view and j.n_pts else None
+        return j
+
+
 class MatchFrame:
     """The parts of a Frame the matchers read (Frame.h). keys: KEYPOINT_DTYPE [n] (mvKeysUn),
     desc: uint8 [n, 32], bounds: (mnMinX, mnMaxX, mnMinY, mnMaxY), uright: float32 [n] or None.
@@ -436,6 +463,58 @@ class ORBmatcher:
                     int(self.mbCheckOrientation), mvp.ctypes.data, nm.ctypes.data, nk.ctypes.data, stream),
                     "SearchByProjection(last frame, batch)")
         return nm, nk, mvp
+
+    # TrackLocalMap's SearchLocalPoints for every frame of a batch extraction in one call, on the device slabs
+    def SearchLocalPointsBatch(self, kps, desc, counts, cap: int, base: int, step: int, uright, geom, jobs, mvp,
+                               mvp_obs, bFarPoints: bool = False, thFarPoints: float = 50.0, model=None, stream=None):
+        """The slabs, uright, geom and stream as SearchByProjectionLastFrameBatch. jobs: LocalMapJob per
+        frame (pose, local map points, th, skip indices). mvp / mvp_obs: int32 [B, cap] host arrays, each
+        frame's mvpMapPoints handles and their Observations() before the search (not modified). model: a
+        CameraModel (pinhole or one KannalaBrandt8 camera), None: the pinhole camera of each job.
+        Returns (nmatches int32 [B], n_to_match int32 [B], n_keys int32 [B], mvp_out int32 [B, cap]); row f
+        equals search_local_points on frame f's keypoints, -1 beyond its count. nmatches[f] is
+        _lib.ORBFE_E_CAPACITY for a frame of more than 2048 keypoints or more than 2048 points in view.
+        Uses self.mfNNratio (0.8 in Tracking::SearchLocalPoints)."""
+        import torch
+        B, cap = len(jobs), int(cap)
+        for t, dt, tail, what in ((kps, torch.int32, (cap, 7), "kps"), (desc, torch.uint8, (cap, 32), "desc"),
+                                  (counts, torch.int32, (2,), "counts")):
+            if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.dim() == len(tail) + 1
+                    and tuple(t.shape[1:]) == tail):
+                raise ValueError(f"{what} must be a contiguous CUDA {dt} tensor of shape [images, {tail}]")
+        nimg = int(counts.shape[0])
+        if kps.shape[0] != nimg or desc.shape[0] != nimg:
+            raise ValueError("kps, desc and counts hold different numbers of images")
+        if base < 0 or step < 0 or (B > 0 and base + (B - 1) * step >= nimg):
+            raise ValueError("base + f * step leaves the slabs")
+        if uright is not None and not (uright.is_cuda and uright.dtype == torch.float32 and uright.is_contiguous()
+                                       and uright.dim() == 2 and uright.shape[0] >= B and uright.shape[1] == cap):
+            raise ValueError("uright must be a contiguous CUDA float32 tensor [frames, cap]")
+        mvp = np.asarray(mvp)
+        mvp_obs = np.asarray(mvp_obs)
+        for a, what in ((mvp, "mvp"), (mvp_obs, "mvp_obs")):
+            if a.dtype != np.int32 or not a.flags.c_contiguous or a.shape != (B, cap):
+                raise ValueError(f"{what} must be a contiguous int32 array [{B}, {cap}]")
+        arr = (LocalMapJob * max(B, 1))()
+        for f, j in enumerate(jobs):
+            if not isinstance(j, LocalMapJob):
+                raise ValueError("jobs must hold LocalMapJob structures")
+            arr[f] = j
+        if stream is None:
+            stream = torch.cuda.current_stream(kps.device).cuda_stream
+        out = np.full((B, cap), -1, np.int32)
+        nm = np.zeros(B, np.int32)
+        ntm = np.zeros(B, np.int32)
+        nk = np.zeros(B, np.int32)
+        if B:
+            with torch.cuda.device(kps.device):
+                _lib.check(self._lib.orbfe_search_local_points_slabs(
+                    kps.data_ptr(), desc.data_ptr(), counts.data_ptr(), cap, int(base), int(step),
+                    uright.data_ptr() if uright is not None else None, geom.ref(),
+                    ctypes.byref(model) if model is not None else None, arr, B, mvp.ctypes.data, mvp_obs.ctypes.data,
+                    int(bool(bFarPoints)), float(thFarPoints), self.mfNNratio, out.ctypes.data, nm.ctypes.data,
+                    ntm.ctypes.data, nk.ctypes.data, stream), "SearchLocalPoints(batch)")
+        return nm, ntm, nk, out
 
     # SearchByProjection(Frame&, KeyFrame*, const set<MapPoint*>&, th, ORBdist) (:1889-2010)
     def SearchByProjectionKeyFrame(self, cur: MatchFrame, mvp, points, th: float, ORBdist: int) -> int:
