@@ -944,6 +944,47 @@ int orbfe_frame_compute_bow(const orbfe_vocabulary* voc, const orbfe_frame* F, i
                             uint32_t* bow_word_ids, double* bow_weights, int32_t* bow_n,
                             uint32_t* fv_node_ids, int32_t* fv_offsets, uint32_t* fv_indices, int32_t* fv_n);
 
+/* SearchByBoW(pKF, F, vpMapPointMatches) (ORBmatcher.cc:223-425) for many (frame, keyframe) jobs in one call
+ * and one kernel launch, one workgroup per job: TrackReferenceKeyFrame's call (Tracking.cc:2836) with one job
+ * per frame of a batch, Relocalization's first loop (Tracking.cc:3680-3701) with several jobs per frame. The
+ * frames are read on the slabs of orbfe_search_by_projection_lastframe_slabs and their FeatureVectors in the
+ * rows orbfe_vocabulary_transform_batch filled for the same images: nothing of a frame visits the host.
+ * Single-camera frames only (two-camera frames: orbfe_search_by_bow_batch). One job: */
+typedef struct orbfe_bow_job {
+    int32_t frame;                 /* batch frame f: image base + f*step of the slabs and of bows */
+    const orbfe_keyframe* kf;      /* resident keyframe; NULL = pKF->isBad(): row all -1, nmatches 0 */
+    const int32_t* kf_mp;          /* host [orbfe_keyframe_n(kf)], bad / NULL points as -1 */
+} orbfe_bow_job;
+
+/* d_kps / d_desc / d_counts / cap / base / step / stream: exactly as orbfe_search_by_projection_lastframe_slabs
+ * (frame f is image base + f*step, N = d_counts[2*image] is read on the device). bows: the arrays
+ * orbfe_vocabulary_transform_batch filled for the same images with row stride cap; only fv_node_ids,
+ * fv_offsets, fv_indices and counts are read, on the device. stream wrote the slabs and bows; the launch runs
+ * on the calling thread's matcher stream after an event recorded there. jobs: any order, a frame may appear
+ * in several; jobs that pass the same kf_mp pointer for the same keyframe share one upload.
+ * Row j of out (host [n_jobs][cap]): slots [0, N) and nmatches[j] are bit-identical to orbfe_search_by_bow on
+ * the host copy of the job's frame, that FeatureVector and the arrays the keyframe handle was made from;
+ * slots [N, cap) are -1; n_keys[j] = N. Rows never affect each other. The row is all -1 with nmatches[j] = 0
+ * for a NULL kf, a keyframe without features or with an empty FeatureVector, N == 0 or fv_n == 0.
+ * Decided on the device, so not refused on the host: a frame whose N is outside [0, min(cap, 4096)] or whose
+ * bow counts are {-1, -1} gives a row of -1 and nmatches[j] = ORBFE_E_CAPACITY; a FeatureVector row whose
+ * offsets or indices leave the frame (not written by the transform) gives a row of -1 and nmatches[j] =
+ * ORBFE_E_ARG; other jobs are unaffected. The results are complete on return, after one host wait.
+ * ORBFE_E_ARG: n_jobs < 0, nframes < 0, a NULL d_kps / d_desc / d_counts / bows / fv_* or counts pointer of
+ * bows / out / nmatches / n_keys, NULL jobs with n_jobs > 0, cap <= 0, a negative base or step, d_desc not
+ * 16-byte aligned, a frame outside [0, nframes), NULL kf_mp for a keyframe with features, a handle of another
+ * device. ORBFE_E_CAPACITY: cap > 8192. Every refusal comes before any device work and before any write to an
+ * output. n_jobs == 0: ORBFE_OK. */
+int orbfe_search_by_bow_slabs(const orbfe_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_counts,
+                              int32_t cap, int32_t base, int32_t step, const orbfe_bow_batch* bows,
+                              const orbfe_bow_job* jobs, int32_t n_jobs, int32_t nframes, float nnratio,
+                              int32_t checkOri, int32_t* out, int32_t* nmatches, int32_t* n_keys, void* stream);
+/* Of this thread's last orbfe_search_by_bow_slabs: out[0] jobs matched with everything staged in LDS, out[1]
+ * jobs with an empty row, out[2] jobs matched with the descriptors, index lists and keyframe pack read in HBM
+ * (they did not fit the call's LDS request), out[3] jobs refused on the device. The workgroup decides and
+ * reports its form. All zero after a refused or empty call. */
+int orbfe_matcher_last_bow_slabs(int32_t* out /* [4] */);
+
 /* ---------------------------------------------------------------------------------------------
  * KeyFrameDatabase for relocalisation (KeyFrameDatabase.cc:39-77, :733-845): the one method of the
  * keyframe database that Tracking calls, Tracking::Relocalization's DetectRelocalizationCandidates.

@@ -174,6 +174,9 @@ _SIGS = {
                                                  _vp, _vp, _c_int, _c_float, _c_float, _vp, _vp, _vp, _vp, _vp]),
     "orbfe_matcher_last_local_batch": (_c_int, [_vp]),
     "orbfe_matcher_last_local_uploads": (_c_int, []),
+    "orbfe_search_by_bow_slabs": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _c_float,
+                                           _c_int, _vp, _vp, _vp, _vp]),
+    "orbfe_matcher_last_bow_slabs": (_c_int, [_vp]),
 }
 
 _lib = None

@@ -1550,3 +1550,6 @@ int orbfe_descriptor_distance(const uint8_t* a, const uint8_t* b) {
 
 // Batched Tracking::SearchLocalPoints (isInFrustum + SearchByProjection(F, local map)) over the same frames.
 #include "orbfe_local_batch.hip"
+
+// Batched SearchByBoW(KF, F) over the same frames and the FeatureVector rows of the batched ComputeBoW.
+#include "orbfe_bow_slabs.hip"

@@ -33,6 +33,43 @@ def _compute_bow(fe, voc, levelsup, stream):
     return voc.transform_batch(fe.desc, fe.counts, levelsup, out=bows, stream=stream)
 
 
+def _track_reference_keyframe(fe, kps, step, jobs, bows, nnratio, check_ori, stream):
+    """ORBmatcher.SearchByBoWSlabs over a front end's slabs (frame f = image f * step) and BowBatch."""
+    from .matcher import ORBmatcher
+    if bows is None:
+        bows = getattr(fe, "_bows", None)
+    if bows is None:
+        raise _lib.OrbfeError("track_reference_keyframe needs the BowBatch of compute_bow(): none was computed")
+    return ORBmatcher(nnratio, check_ori).SearchByBoWSlabs(kps, fe.desc, fe.counts, fe.cap, 0, step, bows, jobs, fe.F,
+                                                           stream=stream)
+
+
+class _SlabRow:
+    """orbfe_frame view (device = 1) of one image's slab row: what orbfe_keyframe_create reads of it."""
+
+    def __init__(self, kps_row, desc_row, n):
+        from .matcher import CFrame
+        self.c = CFrame(n, kps_row.data_ptr(), desc_row.data_ptr(), None, 0.0, 0.0, 0.0, 0.0, 0, None, 0.0, 0, 0, None,
+                        None, 1)
+
+    def ref(self):
+        return ctypes.byref(self.c)
+
+
+def _keyframe(fe, kps, img, bows):
+    """KeyFrameFeatures of slab image img, copied device to device; only the count and the FeatureVector of
+    the image come to the host (which waits for the caller's current torch stream)."""
+    from .matcher import KeyFrameFeatures
+    n = int(fe.counts[img, 0].cpu())
+    if not 0 <= n <= fe.cap:
+        raise _lib.OrbfeError(f"image {img} of the batch has a count outside [0, cap]")
+    if (bows.nimg, bows.cap) != (int(fe.desc.shape[0]), fe.cap):
+        raise ValueError("bows does not hold this front end's images")
+    fv = bows.host_feature_vector(img)
+    with fe.torch.cuda.device(fe.device):
+        return KeyFrameFeatures(_SlabRow(kps[img], fe.desc[img], n), fv)
+
+
 class StereoFrontEnd:
     """`pipelines` > 1 splits the frames into that many sub-batches, each with its own engine handle
     and HIP stream, so the kernels of different sub-batches overlap on the GPU (the latency-bound
@@ -237,6 +274,23 @@ class StereoFrontEnd:
             self.kps, self.desc, self.counts, self.cap, 0, 2, self.uright if self.stereo == "rectified" else None,
             geom, jobs, mvp, mvp_obs, bFarPoints, thFarPoints, model=model, stream=stream)
 
+    def track_reference_keyframe(self, jobs, bows=None, nnratio: float = 0.7, check_ori: bool = True, stream=None):
+        """TrackReferenceKeyFrame's SearchByBoW(mpReferenceKF, mCurrentFrame, ..) (one job per frame) or
+        Relocalization's candidates loop (several jobs per frame) for the frames of the last run() in one
+        launch, on the left-image slabs (image 2f) and the FeatureVector rows of compute_bow(): nothing of a
+        frame is copied to the host. jobs: a list of (frame, KeyFrameFeatures or None, kf_map_points); bows:
+        the BowBatch of compute_bow() (None: the last one). stream: as track_motion_model.
+        -> (nmatches [J], n_keys [J], vpMapPointMatches [J, cap]), see ORBmatcher.SearchByBoWSlabs."""
+        if self.stereo == "fisheye":
+            raise _lib.OrbfeError("track_reference_keyframe searches single-camera frames (stereo 'rectified' or 'none')")
+        return _track_reference_keyframe(self, self.kps, 2, jobs, bows, nnratio, check_ori, stream)
+
+    def keyframe(self, f: int, bows):
+        """Frame f of the last run() as a matcher.KeyFrameFeatures (the next frames' reference keyframe): its
+        left keypoints' angles and descriptors go from the slabs into the keyframe's pack device to device;
+        only its count and its FeatureVector (bows: the BowBatch of compute_bow()) are downloaded."""
+        return _keyframe(self, self.kps, 2 * int(f), bows)
+
     def host_frame(self, f: int):
         """(kps_left structured, desc_left, uright, depth) of frame f, copied to the host."""
         _, kp, d = self.host_image(2 * f)
@@ -321,6 +375,16 @@ class RGBDFrontEnd:
         return ORBmatcher(nnratio).SearchLocalPointsBatch(
             self.keys_un, self.desc, self.counts, self.cap, 0, 1, self.uright, geom, jobs, mvp, mvp_obs, bFarPoints,
             thFarPoints, stream=stream)
+
+    def track_reference_keyframe(self, jobs, bows=None, nnratio: float = 0.7, check_ori: bool = True, stream=None):
+        """StereoFrontEnd.track_reference_keyframe for the F RGB-D frames of the last run() (image f, the
+        undistorted keypoints). Runs after the caller's current torch stream (run()'s) or `stream`.
+        -> (nmatches [J], n_keys [J], vpMapPointMatches [J, cap])."""
+        return _track_reference_keyframe(self, self.keys_un, 1, jobs, bows, nnratio, check_ori, stream)
+
+    def keyframe(self, f: int, bows):
+        """StereoFrontEnd.keyframe for RGB-D frame f (mvKeysUn and mDescriptors of image f)."""
+        return _keyframe(self, self.keys_un, int(f), bows)
 
     def host_frame(self, f: int):
         """(mvKeys, mvKeysUn, mDescriptors, mvuRight, mvDepth) of frame f, copied to the host."""

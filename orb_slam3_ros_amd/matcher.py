@@ -256,6 +256,11 @@ class LocalMapJob(ctypes.Structure):
         return j
 
 
+class BowJob(ctypes.Structure):
+    """struct orbfe_bow_job: one (frame, keyframe) pair of ORBmatcher.SearchByBoWSlabs (24 bytes)."""
+    _fields_ = [("frame", ctypes.c_int32), ("kf", ctypes.c_void_p), ("kf_mp", ctypes.c_void_p)]
+
+
 class MatchFrame:
     """The parts of a Frame the matchers read (Frame.h). keys: KEYPOINT_DTYPE [n] (mvKeysUn),
     desc: uint8 [n, 32], bounds: (mnMinX, mnMaxX, mnMinY, mnMaxY), uright: float32 [n] or None.
@@ -635,6 +640,69 @@ class ORBmatcher:
                 handles, mps, C, F.ref(), f_featvec.ref(), out.ctypes.data, nm.ctypes.data, self.mfNNratio,
                 int(self.mbCheckOrientation)), "SearchByBoW(batch)")
         return nm, out
+
+    # TrackReferenceKeyFrame's / Relocalization's SearchByBoW(pKF, F, ..) for (frame, keyframe) jobs over the
+    # frames of a batch extraction and the FeatureVector rows of the batched ComputeBoW, in one call
+    def SearchByBoWSlabs(self, kps, desc, counts, cap: int, base: int, step: int, bows, jobs, nframes: int,
+                         stream=None):
+        """The slabs and stream as SearchByProjectionLastFrameBatch; frame f is image base + f * step.
+        bows: the vocabulary.BowBatch that transform_batch filled for the same images (same cap). jobs: a list
+        of (frame, KeyFrameFeatures or None, kf_map_points): kf_map_points int32 [kf.N], GetMapPointMatches()
+        handles with bad points as -1 (ignored for None, a discarded keyframe); jobs that pass the same array
+        for the same keyframe share one upload. nframes: the frames the slabs hold.
+        Returns (nmatches int32 [J], n_keys int32 [J], vpMapPointMatches int32 [J, cap]); row j equals
+        SearchByBoW on the host copy of job j's frame, -1 beyond its count. nmatches[j] is
+        _lib.ORBFE_E_CAPACITY for a frame of more than min(cap, 4096) keypoints or without FeatureVector."""
+        import torch
+        J, cap, nframes = len(jobs), int(cap), int(nframes)
+        for t, dt, tail, what in ((kps, torch.int32, (cap, 7), "kps"), (desc, torch.uint8, (cap, 32), "desc"),
+                                  (counts, torch.int32, (2,), "counts")):
+            if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.dim() == len(tail) + 1
+                    and tuple(t.shape[1:]) == tail):
+                raise ValueError(f"{what} must be a contiguous CUDA {dt} tensor of shape [images, {tail}]")
+        nimg = int(counts.shape[0])
+        if kps.shape[0] != nimg or desc.shape[0] != nimg:
+            raise ValueError("kps, desc and counts hold different numbers of images")
+        if base < 0 or step < 0 or nframes < 0 or (nframes > 0 and base + (nframes - 1) * step >= nimg):
+            raise ValueError("base + f * step leaves the slabs")
+        if bows.cap != cap or bows.nimg != nimg:
+            raise ValueError(f"bows must hold the slabs' images: [{nimg}, {cap}], not [{bows.nimg}, {bows.cap}]")
+        if bows.counts.device != kps.device:
+            raise ValueError("bows and the slabs live on different devices")
+        arr = (BowJob * max(J, 1))()
+        keep = []
+        for j, job in enumerate(jobs):
+            f, kf, mp = job
+            if not 0 <= int(f) < nframes:
+                raise ValueError(f"job {j}: frame {f} is outside [0, {nframes})")
+            arr[j].frame = int(f)
+            if kf is None:
+                continue
+            if not isinstance(kf, KeyFrameFeatures) or kf.handle is None:
+                raise ValueError("a job's keyframe is an open KeyFrameFeatures or None")
+            km = _i32(np.ascontiguousarray(mp, np.int32), kf.N, "kf_map_points")
+            keep.append(km)
+            arr[j].kf = kf.handle
+            arr[j].kf_mp = km.ctypes.data if kf.N else None
+        if stream is None:
+            stream = torch.cuda.current_stream(kps.device).cuda_stream
+        out = np.full((J, cap), -1, np.int32)
+        nm = np.zeros(J, np.int32)
+        nk = np.zeros(J, np.int32)
+        if J:
+            with torch.cuda.device(kps.device):
+                _lib.check(self._lib.orbfe_search_by_bow_slabs(
+                    kps.data_ptr(), desc.data_ptr(), counts.data_ptr(), cap, int(base), int(step), bows.ref(), arr, J,
+                    nframes, self.mfNNratio, int(self.mbCheckOrientation), out.ctypes.data, nm.ctypes.data,
+                    nk.ctypes.data, stream), "SearchByBoW(slabs)")
+        return nm, nk, out
+
+    @staticmethod
+    def last_bow_slabs():
+        """(LDS form, empty row, HBM form, refused) job counts of this thread's last SearchByBoWSlabs."""
+        w = np.zeros(4, np.int32)
+        _lib.check(_lib.load().orbfe_matcher_last_bow_slabs(w.ctypes.data), "last_bow_slabs")
+        return tuple(int(v) for v in w)
 
     # SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12) (:765-903)
     def SearchByBoWKF(self, keys1, desc1, map_points1, featvec1: FeatureVector, keys2, desc2, map_points2,

@@ -64,6 +64,16 @@ class BowBatch:
         fv = FeatureVector({int(fid[k]): fidx[foff[k]:foff[k + 1]].tolist() for k in range(nf)})
         return (ids, w), fv
 
+    def host_feature_vector(self, i: int):
+        """Image i's FeatureVector alone, copied to the host (synchronises); the BowVector stays in HBM."""
+        nf = int(self.counts[i, 1].cpu())
+        if nf < 0:
+            raise _lib.OrbfeError(f"image {i} of the batch had a count outside [0, cap]")
+        fid = self.fv_node_ids[i, :nf].cpu().numpy().view(np.uint32)
+        foff = self.fv_offsets[i, :nf + 1].cpu().numpy()
+        fidx = self.fv_indices[i, :int(foff[nf]) if nf else 0].cpu().numpy().view(np.uint32)
+        return FeatureVector({int(fid[k]): fidx[foff[k]:foff[k + 1]].tolist() for k in range(nf)})
+
 
 class ORBVocabulary:
     def __init__(self, handle, lib):
