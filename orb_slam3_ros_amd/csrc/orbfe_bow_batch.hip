@@ -230,20 +230,13 @@ __global__ __launch_bounds__(BB_ANT) void k_bowb_assemble(const int* __restrict_
 
 namespace {
 
-std::atomic<unsigned long long> g_bowb_lds_set{0};   // devices whose k_bowb_assemble may take > 64 KB of LDS
-
 // both launches on s; arguments validated by the caller, the vocabulary's device is current
 int bowb_launch(const orbfe_vocabulary* voc, const uint8_t* d_desc, const int32_t* d_counts, int count_stride, int nimg,
                 int cap, int levelsup, const orbfe_bow_batch* out, hipStream_t s) {
     int pcap = 1;
     while (pcap < cap) pcap <<= 1;
     const size_t lds = (size_t)pcap * 8 + BB_LDS_TAIL;
-    if (lds > 64 * 1024 && voc->device >= 0 && voc->device < 64 &&
-        !(g_bowb_lds_set.load(std::memory_order_acquire) >> voc->device & 1ull)) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bowb_assemble),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BB_MAXN * 8 + BB_LDS_TAIL)));
-        g_bowb_lds_set.fetch_or(1ull << voc->device, std::memory_order_release);
-    }
+    MSCHK(ms_lds_optin<k_bowb_assemble>(voc->device, lds, BB_MAXN * 8 + BB_LDS_TAIL));
     const int empty = voc->n_words == 0 ? 1 : 0;
     int must = 1, norm_l1 = 1;   // ScoringObject.h:74-89
     if (voc->scoring == ORBFE_L2_NORM) norm_l1 = 0;

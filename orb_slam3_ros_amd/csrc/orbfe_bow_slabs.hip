@@ -1,8 +1,8 @@
 // TrackReferenceKeyFrame's and Relocalization's SearchByBoW(pKF, F, vpMapPointMatches) (Tracking.cc:2836,
 // :3680-3701) for many (frame, keyframe) jobs in ONE launch, the frames read where orbfe_extract_batch left
 // them and their FeatureVectors where orbfe_vocabulary_transform_batch left them (included into
-// orbfe_engine.hip's translation unit after orbfe_local_batch.hip, whose slab addressing, completion counter
-// and stream event it shares).
+// orbfe_engine.hip's translation unit after orbfe_local_batch.hip; the slab addressing, the completion and
+// the host scaffold are orbfe_matcher.hip's SlabView, mt_batch_end and ms_* helpers).
 //
 // Workgroup j = job j = (frame f = image base + f * step, resident keyframe). N and the FeatureVector's
 // {bow_n, fv_n} are read on the device, so is the decision how the job runs:
@@ -10,11 +10,9 @@
 //             state staged in LDS, laid out by the actual N and fv_n (k_bow_batch's layout, frame side first);
 //   HBM form  a job that does not fit the call's LDS request keeps only the match state and F's node ids and
 //             offsets in LDS and walks with the descriptors, the index lists, the pack and kf_mp read in place.
-// Both forms are one function (bows_match): each KF node finds its F node by binary search of F's node ids in
-// LDS, bow_walk_node under BowRulesKfF walks it, bow_commit_rows<false> with AngFlat on the pack's angles
-// commits the row. The pointers differ, not the algorithm.
+// Both forms are one function (bow_join_match, k_bow_batch's, with nleft = -1). The pointers differ, not the
+// algorithm.
 #pragma once
-#include <map>
 
 #define BOWS_FORM_LDS 0
 #define BOWS_FORM_EMPTY 1
@@ -31,26 +29,22 @@ struct BowSlabJob {
     int nn, kf_n;
     int frame, live;
 };
-// kps / desc / counts: the extractor's batch outputs; fv_* / bcounts: the orbfe_bow_batch rows of the same
-// images (row stride cap, offsets cap + 1). out: [n_jobs][cap] rows in mapped pinned memory, each slot stored
-// once; res: [n_jobs][3] = {nmatches (or the refusal's code), N, form}. lds: the launch's dynamic LDS bytes;
-// nmax: min(cap, BOWS_NMAX). done / st_host / seq: k_sbp_track_batch's completion counter and sequence word.
+// sl: the extractor's batch outputs (no uright; nmax: min(cap, BOWS_NMAX)); fv_* / bcounts: the
+// orbfe_bow_batch rows of the same images (row stride cap, offsets cap + 1). out: [n_jobs][cap] rows in mapped
+// pinned memory, each slot stored once; res: [n_jobs][3] = {nmatches (or the refusal's code), N, form}. lds:
+// the launch's dynamic LDS bytes. end: the call's completion (mt_batch_end).
 struct BowSlabIn {
-    const OrbKeyPoint* kps;
-    const uint8_t* desc;
-    const int* counts;
+    SlabView sl;
     const uint32_t* fv_nid;
     const int* fv_off;
     const uint32_t* fv_idx;
     const int* bcounts;
-    int cap, base, step, nmax;
     const BowSlabJob* jobs;
     const uint8_t* arena;
     int32_t* out;
     int* res;
-    int* done;
-    int* st_host;
-    int seq, checkOri;
+    BatchEnd end;
+    int checkOri;
     unsigned lds;
     float nnratio;
 };
@@ -65,32 +59,6 @@ __host__ __device__ inline size_t bows_lds_full(int fvn, int nidx, int n, int nv
 }
 __host__ __device__ inline size_t bows_lds_hbm(int fvn, int n) { return bows_meta_lds(fvn) + (size_t)n * 4; }
 
-// The search of one job once its arrays are in place (wherever each of them lives). src is filled with -1,
-// s_hist zeroed, s_n 0, and a barrier has passed. On return s_n holds nmatches and a barrier has passed.
-__device__ __forceinline__ void bows_match(const unsigned* knid, const int* kfo, const int* kfi, const float* kang,
-                                           const uint4* kd, const int* mp, int nn, const unsigned* s_fnid,
-                                           const int* s_fo, const int* fi, const uint4* fd, int* s_src, int fvn, int n,
-                                           const float (&fang)[MT_BOW_FR], float nnratio, int checkOri, int* out,
-                                           int* s_hist, unsigned* s_keep, int* s_n) {
-    const int tid = threadIdx.x;
-    const BowRulesKfF rules{mp, s_src, -1, nnratio};
-    for (int a = tid >> 2; a < nn; a += MT_BOW_NT / 4) {   // one quad per KF node
-        const unsigned id = knid[a];
-        int b = 0, hi = fvn;   // lower_bound of the node id among F's (the quad's lanes agree)
-        while (b < hi) {
-            const int mid = (b + hi) >> 1;
-            if (s_fnid[mid] < id) b = mid + 1;
-            else hi = mid;
-        }
-        if (b >= fvn || s_fnid[b] != id) continue;
-        bow_walk_node(kfo[a], kfo[a + 1], s_fo[b], s_fo[b + 1], kfi, fi, kd, fd, tid & 3, rules);
-    }
-    SYNC();
-    bow_commit_rows<false>(n, s_src, [&](int u, int) { return fang[u]; }, AngFlat{kang}, mp, checkOri, out, s_hist,
-                           s_keep, s_n);
-    SYNC();
-}
-
 __global__ __launch_bounds__(MT_BOW_NT) void k_bow_slabs(BowSlabIn in) {
     extern __shared__ __attribute__((aligned(16))) uint8_t bs_sm[];
     __shared__ int s_hist[MT_HISTO];
@@ -100,13 +68,13 @@ __global__ __launch_bounds__(MT_BOW_NT) void k_bow_slabs(BowSlabIn in) {
     // every lane reads the same record and the same counts: the form and every branch and trip count below
     // are workgroup-uniform, so the whole workgroup reaches every SYNC() of the path it takes
     const BowSlabJob jb = in.jobs[j];
-    const int img = in.base + jb.frame * in.step;
-    const int N = in.counts[2 * img];
+    const int cap = in.sl.cap, img = in.sl.image(jb.frame);
+    const int N = in.sl.count(img);
     const int bown = in.bcounts[2 * img], fvn = in.bcounts[2 * img + 1];
-    const int* g_fo = in.fv_off + (size_t)img * ((size_t)in.cap + 1);
-    int* out = in.out + (size_t)j * in.cap;
+    const int* g_fo = in.fv_off + (size_t)img * ((size_t)cap + 1);
+    int* out = in.out + (size_t)j * cap;
     int form, nm = 0, nidx = 0;
-    const bool over = N < 0 || N > in.nmax || bown < 0 || fvn < 0;
+    const bool over = in.sl.over(N) || bown < 0 || fvn < 0;
     if (!jb.live || (!over && (N == 0 || fvn == 0))) {
         form = BOWS_FORM_EMPTY;
     } else if (over) {
@@ -125,16 +93,16 @@ __global__ __launch_bounds__(MT_BOW_NT) void k_bow_slabs(BowSlabIn in) {
     }
     if (form == BOWS_FORM_LDS || form == BOWS_FORM_HBM) {
         // F's angles for the commit, loaded now (their latency hides under the staging and the walks)
-        const OrbKeyPoint* fkeys = in.kps + (size_t)img * in.cap;
+        const OrbKeyPoint* fkeys = in.sl.keys_of(img);
         float fang[MT_BOW_FR];
 #pragma unroll
         for (int u = 0; u < MT_BOW_FR; u++) {
             const int i = tid + u * MT_BOW_NT;
             fang[u] = i < N ? fkeys[i].angle : 0.f;
         }
-        const uint32_t* g_fnid = in.fv_nid + (size_t)img * in.cap;
-        const uint32_t* g_fi = in.fv_idx + (size_t)img * in.cap;
-        const uint4* g_fd = (const uint4*)(in.desc + (size_t)img * in.cap * 32);
+        const uint32_t* g_fnid = in.fv_nid + (size_t)img * cap;
+        const uint32_t* g_fi = in.fv_idx + (size_t)img * cap;
+        const uint4* g_fd = (const uint4*)in.sl.desc_of(img);
         const int* g_mp = (const int*)(in.arena + jb.o_mp);
         const uint8_t* pk = (const uint8_t*)jb.pack;
         unsigned* s_fnid = (unsigned*)bs_sm;
@@ -169,10 +137,10 @@ __global__ __launch_bounds__(MT_BOW_NT) void k_bow_slabs(BowSlabIn in) {
             bad = __syncthreads_or(bad);
             if (!bad) {
                 const uint8_t* sk = (const uint8_t*)s_kf;
-                bows_match((const unsigned*)sk, (const int*)(sk + jb.o_off), (const int*)(sk + jb.o_idx),
-                           (const float*)(sk + jb.o_ang), (const uint4*)(sk + jb.o_desc), (const int*)s_mpw, jb.nn,
-                           s_fnid, s_fo, s_fi, s_fd, s_src, fvn, N, fang, in.nnratio, in.checkOri, out, s_hist,
-                           &s_keep, &s_n);
+                bow_join_match((const unsigned*)sk, (const int*)(sk + jb.o_off), (const int*)(sk + jb.o_idx),
+                               (const float*)(sk + jb.o_ang), (const uint4*)(sk + jb.o_desc), (const int*)s_mpw, jb.nn,
+                               s_fnid, s_fo, s_fi, s_fd, s_src, fvn, N, -1, fang, in.nnratio, in.checkOri, out, s_hist,
+                               &s_keep, &s_n);
             }
         } else {
             int* s_src = (int*)s_rest;
@@ -180,22 +148,22 @@ __global__ __launch_bounds__(MT_BOW_NT) void k_bow_slabs(BowSlabIn in) {
             for (int i = tid; i < N; i += MT_BOW_NT) s_src[i] = -1;
             bad = __syncthreads_or(bad);
             if (!bad)
-                bows_match((const unsigned*)pk, (const int*)(pk + jb.o_off), (const int*)(pk + jb.o_idx),
-                           (const float*)(pk + jb.o_ang), (const uint4*)(pk + jb.o_desc), g_mp, jb.nn, s_fnid, s_fo,
-                           (const int*)g_fi, g_fd, s_src, fvn, N, fang, in.nnratio, in.checkOri, out, s_hist, &s_keep,
-                           &s_n);
+                bow_join_match((const unsigned*)pk, (const int*)(pk + jb.o_off), (const int*)(pk + jb.o_idx),
+                               (const float*)(pk + jb.o_ang), (const uint4*)(pk + jb.o_desc), g_mp, jb.nn, s_fnid, s_fo,
+                               (const int*)g_fi, g_fd, s_src, fvn, N, -1, fang, in.nnratio, in.checkOri, out, s_hist,
+                               &s_keep, &s_n);
         }
         if (bad) {
             form = BOWS_FORM_REFUSED;
             nm = ORBFE_E_ARG;
         } else {
             nm = s_n;
-            for (int i = N + tid; i < in.cap; i += MT_BOW_NT) out[i] = -1;
+            for (int i = N + tid; i < cap; i += MT_BOW_NT) out[i] = -1;
         }
     }
     if (form == BOWS_FORM_EMPTY || form == BOWS_FORM_REFUSED)
-        for (int i = tid; i < in.cap; i += MT_BOW_NT) out[i] = -1;
-    // every wave's row stores complete, the barrier, then this workgroup's release (as k_sbp_track_batch)
+        for (int i = tid; i < cap; i += MT_BOW_NT) out[i] = -1;
+    // every wave's row stores complete, the barrier, then this workgroup's release (mt_batch_end)
     __builtin_amdgcn_s_waitcnt(0);
     SYNC();
     if (tid == 0) {
@@ -203,27 +171,13 @@ __global__ __launch_bounds__(MT_BOW_NT) void k_bow_slabs(BowSlabIn in) {
         co[0] = nm;
         co[1] = N;
         co[2] = form;
-        __threadfence_system();
-        const int before = __hip_atomic_fetch_add(in.done, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (before == (int)gridDim.x - 1) {
-            __threadfence_system();
-            volatile int* st = in.st_host;
-            st[0] = 0;
-            st[1] = (int)gridDim.x;
-            st[2] = 0;
-            st[3] = 0;
-            st[5] = 0;
-            __threadfence_system();
-            st[4] = in.seq;
-            __threadfence_system();
-        }
+        mt_batch_end(in.end);
     }
 }
 
 namespace {
 // orbfe_matcher_last_bow_slabs: jobs in the LDS form, with an empty row, in the HBM form, refused
 thread_local int t_bow_slabs[4] = {0, 0, 0, 0};
-std::atomic<unsigned long long> g_bows_lds_set{0};   // devices whose k_bow_slabs may take > 64 KB of LDS
 constexpr size_t kBowSlabsLdsMax = 150 * 1024;       // orbfe_search_by_bow_batch's bound
 }  // namespace
 
@@ -236,10 +190,9 @@ int orbfe_search_by_bow_slabs(const orbfe_keypoint* d_kps, const uint8_t* d_desc
     t_bow_slabs[0] = t_bow_slabs[1] = t_bow_slabs[2] = t_bow_slabs[3] = 0;
     // every refusal below comes before any device work and before any write to the outputs
     if (n_jobs < 0 || nframes < 0) return ORBFE_E_ARG;
-    if (!d_kps || !d_desc || !d_counts || !bows || !bows->fv_node_ids || !bows->fv_offsets || !bows->fv_indices ||
-        !bows->counts || !out || !nmatches || !n_keys || (n_jobs > 0 && !jobs))
+    if (!slabs_ok(d_kps, d_desc, d_counts, cap, base, step) || !bows || !bows->fv_node_ids || !bows->fv_offsets ||
+        !bows->fv_indices || !bows->counts || !out || !nmatches || !n_keys || (n_jobs > 0 && !jobs))
         return ORBFE_E_ARG;
-    if (cap <= 0 || base < 0 || step < 0) return ORBFE_E_ARG;
     if ((uintptr_t)d_desc & 15) return ORBFE_E_ARG;   // staged with 16-byte loads
     bool any = false;
     for (int j = 0; j < n_jobs; j++) {
@@ -249,7 +202,7 @@ int orbfe_search_by_bow_slabs(const orbfe_keypoint* d_kps, const uint8_t* d_desc
         any = any || b.kf;
     }
     if (cap > BB_MAXN) return ORBFE_E_CAPACITY;
-    if ((size_t)n_jobs * (size_t)cap > ((size_t)1 << 26)) return ORBFE_E_CAPACITY;
+    if (!slab_rows_ok(n_jobs, cap)) return ORBFE_E_CAPACITY;
     if (n_jobs == 0) return ORBFE_OK;
     if (any) {   // a handle belongs to its create's device
         int dev = 0;
@@ -263,7 +216,7 @@ int orbfe_search_by_bow_slabs(const orbfe_keypoint* d_kps, const uint8_t* d_desc
     const int nmax = std::min<int>(cap, BOWS_NMAX);
     Plan p;
     std::vector<BowSlabJob> bj(n_jobs);
-    std::map<std::pair<const void*, const void*>, size_t> shared;
+    UploadOnce shared;
     int max_nvec = 0, max_kfn = 0;
     for (int j = 0; j < n_jobs; j++) {
         const orbfe_keyframe* k = jobs[j].kf;
@@ -271,11 +224,8 @@ int orbfe_search_by_bow_slabs(const orbfe_keypoint* d_kps, const uint8_t* d_desc
         memset(&t, 0, sizeof(t));
         t.frame = jobs[j].frame;
         if (!k || !k->bow) continue;   // NULL, no features or an empty FeatureVector: the empty row
-        const auto key = std::make_pair((const void*)jobs[j].kf_mp, (const void*)k);
-        auto it = shared.find(key);
-        if (it == shared.end()) it = shared.emplace(key, p.upload(jobs[j].kf_mp, (size_t)k->n * 4)).first;
         t.pack = (const uint4*)k->pack;
-        t.o_mp = it->second;
+        t.o_mp = shared(p, jobs[j].kf_mp, (uintptr_t)k, (size_t)k->n * 4);
         t.nvec = k->nvec;
         t.o_off = k->o_off; t.o_idx = k->o_idx; t.o_ang = k->o_ang; t.o_desc = k->o_desc;
         t.nn = k->nn;
@@ -285,46 +235,26 @@ int orbfe_search_by_bow_slabs(const orbfe_keypoint* d_kps, const uint8_t* d_desc
         max_kfn = std::max(max_kfn, k->n);
     }
     const size_t o_jobs = p.upload(bj.data(), (size_t)n_jobs * sizeof(BowSlabJob));
-    const int zero = 0;
-    const size_t o_done = p.upload(&zero, 4);
+    const size_t o_done = ms_plan_done(p);
     const size_t lds = std::min(kBowSlabsLdsMax, bows_lds_full(nmax, nmax, nmax, max_nvec, max_kfn));
     const size_t nrow = (size_t)n_jobs * cap, nout = nrow + 3 * (size_t)n_jobs;   // the rows, then {nm, N, form}
-    MSCHK(ms_prepare(p));
-    MSCHK(ms_out_block(nout, std::max<size_t>(nout + nout / 2, 2048)));
-    MatchScratch& m = t_ms;
-    hipStream_t s = m.stream;
-    if (lds > 64 * 1024 && m.device >= 0 && m.device < 64 &&
-        !(g_bows_lds_set.load(std::memory_order_acquire) >> m.device & 1ull)) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bow_slabs),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBowSlabsLdsMax));
-        g_bows_lds_set.fetch_or(1ull << m.device, std::memory_order_release);
-    }
-    // the slabs and the FeatureVectors were written on the caller's stream: the launch waits for an event
-    // recorded there
-    if (t_track_ev_dev != m.device) {
-        HIPCHK(hipEventCreateWithFlags(&t_track_ev, hipEventDisableTiming));
-        t_track_ev_dev = m.device;
-    }
-    HIPCHK(hipEventRecord(t_track_ev, (hipStream_t)stream));
-    HIPCHK(hipStreamWaitEvent(s, t_track_ev, 0));
-    MsTimer timer(s);
     BowSlabIn in;
     memset(&in, 0, sizeof(in));
-    in.kps = (const OrbKeyPoint*)d_kps;
-    in.desc = d_desc;
-    in.counts = d_counts;
+    MSCHK(ms_batch_prepare(p, nout, o_done, in.end));
+    MatchScratch& m = t_ms;
+    hipStream_t s = m.stream;
+    MSCHK(ms_lds_optin<k_bow_slabs>(m.device, lds, kBowSlabsLdsMax));
+    MSCHK(ms_after_caller(stream));   // the slabs and the FeatureVectors were written on the caller's stream
+    MsTimer timer(s);
+    in.sl = SlabView{(const OrbKeyPoint*)d_kps, d_desc, d_counts, nullptr, cap, base, step, nmax};
     in.fv_nid = bows->fv_node_ids;
     in.fv_off = bows->fv_offsets;
     in.fv_idx = bows->fv_indices;
     in.bcounts = bows->counts;
-    in.cap = cap; in.base = base; in.step = step; in.nmax = nmax;
     in.jobs = ms_ptr<const BowSlabJob>(o_jobs);
     in.arena = ms_ptr<const uint8_t>(0);
     in.out = m.ho_dev;
     in.res = m.ho_dev + nrow;
-    in.done = ms_ptr<int>(o_done);
-    in.st_host = m.hs_dev;
-    in.seq = ++m.seq;
     in.checkOri = checkOri ? 1 : 0;
     in.lds = (unsigned)lds;
     in.nnratio = nnratio;
@@ -332,7 +262,7 @@ int orbfe_search_by_bow_slabs(const orbfe_keypoint* d_kps, const uint8_t* d_desc
     hipLaunchKernelGGL(k_bow_slabs, dim3(n_jobs), dim3(MT_BOW_NT), lds, s, in);
     HIPCHK(hipGetLastError());
     timer.end();
-    MSCHK(ms_wait_seq(s, in.seq));
+    MSCHK(ms_wait_seq(s, in.end.seq));
     memcpy(out, m.ho, nrow * 4);   // complete: the sequence word comes after every workgroup's release
     for (int j = 0; j < n_jobs; j++) {
         const int* co = m.ho + nrow + 3 * (size_t)j;

@@ -1,7 +1,7 @@
 // TrackLocalMap's SearchLocalPoints (Tracking.cc:3382-3452) for the frames of a batch extraction in ONE
 // launch, read where orbfe_extract_batch and orbfe_stereo_match_batch left them (included into
-// orbfe_engine.hip's translation unit after orbfe_track_batch.hip, whose slab addressing, completion counter
-// and stream event it shares).
+// orbfe_engine.hip's translation unit after orbfe_track_batch.hip; the slab addressing, the completion and
+// the host scaffold are orbfe_matcher.hip's SlabView, mt_batch_end and ms_* helpers).
 //
 // Workgroup f = frame f = image base + f * step of the slabs, in two phases:
 //   A  Frame::isInFrustum + MapPoint::PredictScale over the job's points (mt_frustum_single, the code
@@ -13,7 +13,6 @@
 // Frames are independent: each has its own pose, points (or a shared upload with its own skip bitset), th
 // and slot row.
 #pragma once
-#include <map>
 
 #define LOC_MAX_POINTS ORBFE_LOCAL_BATCH_MAX_POINTS
 
@@ -29,14 +28,10 @@ struct LocJob {
 // rows_in / obs_in: the uploaded mvp_in / mvp_obs [nframes][cap]; rows: the working rows in HBM; mvp_out:
 // the same rows in mapped pinned memory, each slot stored once, after the search. counts_out:
 // [nframes][4] = {assigned (ORBFE_E_CAPACITY: more keypoints or more points in view than the workgroup
-// holds), dropped, N, nToMatch}. done / st_host / seq: k_sbp_track_batch's completion counter and
-// sequence word.
+// holds), dropped, N, nToMatch}. sl: the extractor's batch outputs; end: the call's completion
+// (mt_batch_end).
 struct LocIn {
-    const OrbKeyPoint* kps;
-    const uint8_t* desc;
-    const int* counts;
-    const float* uright;
-    int cap, base, step, nmax;
+    SlabView sl;
     const LocJob* jobs;
     uint8_t* arena;
     const int32_t* rows_in;
@@ -45,24 +40,23 @@ struct LocIn {
     int32_t* mvp_out;
     int* counts_out;
     int32_t* view_out;
-    int* done;
-    int* st_host;
-    int seq, bFar;
+    BatchEnd end;
+    int bFar;
     float thFar, nnratio;
 };
 __global__ __launch_bounds__(MT_BLK_NT) void k_local_batch(FrameDev fr0, BlkGeom gm, LocIn in) {
     extern __shared__ __attribute__((aligned(16))) uint8_t mt_sm[];
     __shared__ int s_wtot[MT_BLK_NT / 64];
     const int tid = threadIdx.x, f = blockIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int img = in.base + f * in.step;
-    const int N = in.counts[2 * img];   // (uniform over the workgroup)
+    const int cap = in.sl.cap, img = in.sl.image(f);
+    const int N = in.sl.count(img);   // (uniform over the workgroup)
     const LocJob& jb = in.jobs[f];
     const int np = jb.n_pts;
     // the row starts as mvp_in's (a search leaves the slots it does not assign alone), -1 beyond the frame
-    int32_t* row = in.rows + (size_t)f * in.cap;
-    const int32_t* row_in = in.rows_in + (size_t)f * in.cap;
-    const int nheld = min(max(N, 0), in.cap);
-    for (int k = tid; k < in.cap; k += MT_BLK_NT) row[k] = k < nheld ? row_in[k] : -1;
+    int32_t* row = in.rows + (size_t)f * cap;
+    const int32_t* row_in = in.rows_in + (size_t)f * cap;
+    const int nheld = min(max(N, 0), cap);
+    for (int k = tid; k < cap; k += MT_BLK_NT) row[k] = k < nheld ? row_in[k] : -1;
     // ---- phase A: the points in view, compacted in array order ----
     const orbfe_map_point_3d* pts = (const orbfe_map_point_3d*)(in.arena + jb.o_pts);
     const uint32_t* skip = jb.o_skip != ~(size_t)0 ? (const uint32_t*)(in.arena + jb.o_skip) : nullptr;
@@ -97,18 +91,14 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_local_batch(FrameDev fr0, BlkGeom
         nview += all;
         SYNC();   // s_wtot is rewritten by the next trip
     }
-    const bool over = N < 0 || N > in.nmax || nview > MT_BLOCK_MAXQ;
+    const bool over = in.sl.over(N) || nview > MT_BLOCK_MAXQ;
     const int* cnt = nullptr;
     // the row's fill and the records are complete before any thread reads them
     __builtin_amdgcn_s_waitcnt(0);
     SYNC();
     // ---- phase B: SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints) on the records ----
     if (nview > 0 && N > 0 && !over) {
-        FrameDev fr = fr0;
-        fr.n = N;
-        fr.keys = in.kps + (size_t)img * in.cap;
-        fr.desc = (const uint32_t*)(in.desc + (size_t)img * in.cap * 32);
-        fr.uright = in.uright ? in.uright + (size_t)f * in.cap : nullptr;
+        const FrameDev fr = in.sl.frame(fr0, f, img, N);
         const float th = jb.th;
         int qid[MT_BLK_QPT];
         float qang[MT_BLK_QPT];
@@ -124,13 +114,13 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_local_batch(FrameDev fr0, BlkGeom
             qid[i] = recs[q].id;
             QS[i] = blk_load<0>(fr, recs, q, th, in.bFar, 0, in.thFar);
         }
-        const BlkIO io{row, in.obs_in + (size_t)f * in.cap, row, 0, 0, 0, 0, nullptr, nullptr, 0, nullptr, nullptr};
+        const BlkIO io{row, in.obs_in + (size_t)f * cap, row, 0, 0, 0, 0, nullptr, nullptr, 0, nullptr, nullptr};
         blk_search<0>(fr, gm, QS, qid, qang, nview, in.nnratio, 0, 1, io, mt_sm,
                       [&](int q) { return blk_load<0>(fr, recs, q, th, in.bFar, 0, in.thFar); }, cnt);
     }
     // the row to the host, each slot once (blk_search ended with its stores complete and a barrier)
-    int32_t* out = in.mvp_out + (size_t)f * in.cap;
-    for (int k = tid; k < in.cap; k += MT_BLK_NT) out[k] = row[k];
+    int32_t* out = in.mvp_out + (size_t)f * cap;
+    for (int k = tid; k < cap; k += MT_BLK_NT) out[k] = row[k];
     __builtin_amdgcn_s_waitcnt(0);
     SYNC();
     if (tid == 0) {
@@ -139,21 +129,7 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_local_batch(FrameDev fr0, BlkGeom
         co[1] = cnt ? cnt[1] : 0;
         co[2] = N;
         co[3] = nview;
-        // this workgroup's row, view bits and counts are released at system scope before it is counted
-        __threadfence_system();
-        const int before = __hip_atomic_fetch_add(in.done, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (before == (int)gridDim.x - 1) {
-            __threadfence_system();
-            volatile int* st = in.st_host;
-            st[0] = 0;
-            st[1] = (int)gridDim.x;
-            st[2] = 0;
-            st[3] = 0;
-            st[5] = 0;
-            __threadfence_system();
-            st[4] = in.seq;
-            __threadfence_system();
-        }
+        mt_batch_end(in.end);   // this workgroup's row, view bits and counts are released before it is counted
     }
 }
 
@@ -178,12 +154,11 @@ int orbfe_search_local_points_slabs(const orbfe_keypoint* d_kps, const uint8_t* 
     // every refusal below comes before any device work and before any write to the outputs
     if (nframes < 0) return ORBFE_E_ARG;
     if (nframes == 0) return ORBFE_OK;
-    if (!d_kps || !d_desc || !d_counts || !geom || !jobs || !mvp_in || !mvp_obs || !mvp_out || !nmatches ||
-        !n_to_match || !n_keys)
+    if (!slabs_ok(d_kps, d_desc, d_counts, cap, base, step) || !geom || !jobs || !mvp_in || !mvp_obs || !mvp_out ||
+        !nmatches || !n_to_match || !n_keys)
         return ORBFE_E_ARG;
-    if (cap <= 0 || base < 0 || step < 0) return ORBFE_E_ARG;
     if (geom->two_cams || geom->nlevels <= 0 || !geom->scale_factors) return ORBFE_E_ARG;
-    if (model && model->type != ORBFE_CAM_PINHOLE && model->type != ORBFE_CAM_KANNALA_BRANDT8) return ORBFE_E_ARG;
+    if (model && !cam_model_ok(model)) return ORBFE_E_ARG;
     for (int f = 0; f < nframes; f++) {
         const orbfe_local_job& j = jobs[f];
         if (j.n_pts < 0 || j.n_skip < 0 || (j.n_pts > 0 && !j.pts) || (j.n_skip > 0 && !j.skip)) return ORBFE_E_ARG;
@@ -198,7 +173,7 @@ int orbfe_search_local_points_slabs(const orbfe_keypoint* d_kps, const uint8_t* 
     G.n = nmax;
     BlkGeom gm;
     if (!blk_geom(&G, gm)) return ORBFE_E_CAPACITY;
-    if ((size_t)nframes * (size_t)cap > ((size_t)1 << 26)) return ORBFE_E_CAPACITY;
+    if (!slab_rows_ok(nframes, cap)) return ORBFE_E_CAPACITY;
     // one upload for the call: the scale factors, every distinct point array, the skip bitsets, the slot
     // rows and their Observations, the job table and the zeroed completion counter
     orbfe_stereo_rig rig;
@@ -208,7 +183,7 @@ int orbfe_search_local_points_slabs(const orbfe_keypoint* d_kps, const uint8_t* 
     const size_t o_scale = p.upload(geom->scale_factors, (size_t)geom->nlevels * 4);
     std::vector<LocJob> lj(nframes);
     std::vector<std::vector<uint32_t>> bits(nframes);
-    std::map<std::pair<const void*, int>, size_t> shared;
+    UploadOnce shared;
     size_t nview_words = 0;
     for (int f = 0; f < nframes; f++) {
         const orbfe_local_job& j = jobs[f];
@@ -220,11 +195,7 @@ int orbfe_search_local_points_slabs(const orbfe_keypoint* d_kps, const uint8_t* 
         t.o_skip = ~(size_t)0;
         t.view = -1;
         if (j.n_pts == 0) continue;
-        const auto key = std::make_pair((const void*)j.pts, (int)j.n_pts);
-        auto it = shared.find(key);
-        if (it == shared.end())
-            it = shared.emplace(key, p.upload(j.pts, (size_t)j.n_pts * sizeof(orbfe_map_point_3d))).first;
-        t.o_pts = it->second;
+        t.o_pts = shared(p, j.pts, (uintptr_t)j.n_pts, (size_t)j.n_pts * sizeof(orbfe_map_point_3d));
         if (j.n_skip > 0) {
             bits[f].assign(((size_t)j.n_pts + 31) / 32, 0u);
             for (int k = 0; k < j.n_skip; k++) bits[f][j.skip[k] >> 5] |= 1u << (j.skip[k] & 31);
@@ -238,8 +209,7 @@ int orbfe_search_local_points_slabs(const orbfe_keypoint* d_kps, const uint8_t* 
     const size_t nrow = (size_t)nframes * cap;
     const size_t o_rows_in = p.upload(mvp_in, nrow * 4);
     const size_t o_obs_in = p.upload(mvp_obs, nrow * 4);
-    const int zero = 0;
-    const size_t o_done = p.upload(&zero, 4);
+    const size_t o_done = ms_plan_done(p);
     // (the job table is uploaded last: it holds the scratch offsets, which follow every upload)
     const size_t o_jobs = p.upload(lj.data(), (size_t)nframes * sizeof(LocJob));
     const size_t o_rows = p.scratch(nrow * 4);
@@ -247,35 +217,16 @@ int orbfe_search_local_points_slabs(const orbfe_keypoint* d_kps, const uint8_t* 
         if (lj[f].n_pts > 0)
             lj[f].o_recs = p.scratch((size_t)std::min<int>(lj[f].n_pts, MT_BLOCK_MAXQ) * sizeof(orbfe_map_point));
     const size_t nout = nrow + 4 * (size_t)nframes + nview_words;   // the rows, the counts, the view bits
-    MSCHK(ms_prepare(p));
-    MSCHK(ms_out_block(nout, std::max<size_t>(nout + nout / 2, 2048)));
-    t_local_uploads = (int)shared.size();
-    MatchScratch& m = t_ms;
-    hipStream_t s = m.stream;
-    // the slabs were written on the caller's stream: the launch waits for an event recorded there
-    if (t_track_ev_dev != m.device) {
-        HIPCHK(hipEventCreateWithFlags(&t_track_ev, hipEventDisableTiming));
-        t_track_ev_dev = m.device;
-    }
-    HIPCHK(hipEventRecord(t_track_ev, (hipStream_t)stream));
-    HIPCHK(hipStreamWaitEvent(s, t_track_ev, 0));
-    MsTimer timer(s);
-    FrameDev fr;
-    memset(&fr, 0, sizeof(fr));
-    fr.minx = geom->min_x; fr.maxx = geom->max_x; fr.miny = geom->min_y; fr.maxy = geom->max_y;
-    fr.invw = static_cast<float>(ORBFE_GRID_COLS) / (geom->max_x - geom->min_x);
-    fr.invh = static_cast<float>(ORBFE_GRID_ROWS) / (geom->max_y - geom->min_y);
-    fr.mbf = geom->mbf;
-    fr.nlevels = geom->nlevels;
-    fr.scale = ms_ptr<const float>(o_scale);
-    fr.nleft = -1;
     LocIn in;
     memset(&in, 0, sizeof(in));
-    in.kps = (const OrbKeyPoint*)d_kps;
-    in.desc = d_desc;
-    in.counts = d_counts;
-    in.uright = d_uright;
-    in.cap = cap; in.base = base; in.step = step; in.nmax = nmax;
+    MSCHK(ms_batch_prepare(p, nout, o_done, in.end));
+    t_local_uploads = (int)shared.seen.size();
+    MatchScratch& m = t_ms;
+    hipStream_t s = m.stream;
+    MSCHK(ms_after_caller(stream));
+    MsTimer timer(s);
+    const FrameDev fr = ms_geom_frame(geom, o_scale);
+    in.sl = SlabView{(const OrbKeyPoint*)d_kps, d_desc, d_counts, d_uright, cap, base, step, nmax};
     in.jobs = ms_ptr<const LocJob>(o_jobs);
     in.arena = ms_ptr<uint8_t>(0);
     in.rows_in = ms_ptr<const int32_t>(o_rows_in);
@@ -284,9 +235,6 @@ int orbfe_search_local_points_slabs(const orbfe_keypoint* d_kps, const uint8_t* 
     in.mvp_out = m.ho_dev;
     in.counts_out = m.ho_dev + nrow;
     in.view_out = m.ho_dev + nrow + 4 * (size_t)nframes;
-    in.done = ms_ptr<int>(o_done);
-    in.st_host = m.hs_dev;
-    in.seq = ++m.seq;
     in.bFar = bFarPoints ? 1 : 0;
     in.thFar = thFarPoints;
     in.nnratio = nnratio;
@@ -294,7 +242,7 @@ int orbfe_search_local_points_slabs(const orbfe_keypoint* d_kps, const uint8_t* 
     hipLaunchKernelGGL(k_local_batch, dim3(nframes), dim3(MT_BLK_NT), blk_lds(nmax, geom->nlevels, gm), s, fr, gm, in);
     HIPCHK(hipGetLastError());
     timer.end();
-    MSCHK(ms_wait_seq(s, in.seq));
+    MSCHK(ms_wait_seq(s, in.end.seq));
     memcpy(mvp_out, m.ho, nrow * 4);   // complete: the sequence word comes after every workgroup's release
     for (int f = 0; f < nframes; f++) {
         const int* co = m.ho + nrow + 4 * (size_t)f;

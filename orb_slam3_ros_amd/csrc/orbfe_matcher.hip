@@ -15,6 +15,7 @@
 #pragma once
 #include "glibc_atan2f.h"
 #include "glibc_logf.h"
+#include <map>
 #include <memory>
 
 #define MT_NT 256
@@ -44,6 +45,82 @@ struct FrameDev {
     int nleft;              // -1: single camera
     const int* l2r;         // mvLeftToRightMatch [nleft]
     const int* r2l;         // mvRightToLeftMatch [n - nleft]
+};
+
+// ---- The zero-copy hand-off to the host, device side. Every kernel that ends a call without a stream
+// synchronisation publishes through these two functions; the host side is host_seq_acquire / ms_wait_seq.
+//
+// mt_publish_status: ONE thread stores the status words of a call into mapped pinned memory, the sequence
+// word st[4] last. The caller has made the workgroup's result stores complete and passed a barrier
+// (`s_waitcnt(0); SYNC();`), so they precede this thread in program order. Then:
+//   fence 1  releases those results, and whatever the caller wrote since (io.stats[2]), at system scope
+//            before any status word: a host that sees a status word sees the results;
+//   fence 2  orders the words before st[4]. The host's spin is an ACQUIRE load of st[4]
+//            (host_seq_acquire), which pairs with this fence: once it reads `seq`, its later reads of the
+//            words and of the result block cannot see older values;
+//   fence 3  pushes st[4] out before the thread retires, so the spinning host is not left waiting for
+//            the end of the kernel.
+// One release by one thread: a release per thread wrote back the L2 once per wave and cost more than the
+// searches. NW words are written: 5 = st[0..3] and st[5], 4 = st[0..3], 2 = st[0..1]; a call's driver
+// reads no word its kernel does not write.
+template <int NW = 5>
+__device__ __forceinline__ void mt_publish_status(volatile int* st, int seq, int w0, int w1, int w2 = 0, int w3 = 0,
+                                                  int w5 = 0) {
+    __threadfence_system();
+    st[0] = w0;
+    st[1] = w1;
+    if (NW > 2) {
+        st[2] = w2;
+        st[3] = w3;
+    }
+    if (NW > 4) st[5] = w5;
+    __threadfence_system();
+    st[4] = seq;
+    __threadfence_system();
+}
+// mt_block_done: ONE thread counts its workgroup done on a counter the call zeroed; true for the last of
+// the grid, which then publishes. The system-scope release comes BEFORE the count: this workgroup's
+// rows and counts (mapped pinned memory) must be on their way to the host before any workgroup can learn
+// that all are done. The count is ACQ_REL at agent scope: the last workgroup's increment is ordered after
+// every other workgroup's, so its publish follows every release.
+__device__ __forceinline__ bool mt_block_done(int* done) {
+    __threadfence_system();
+    return __hip_atomic_fetch_add(done, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
+}
+// What a batch kernel needs to end its call: the zeroed counter, the status words, the sequence number
+// (host side: ms_plan_done / ms_batch_prepare). The last workgroup reports {0, workgroups, 0, 0, 0}.
+struct BatchEnd {
+    int* done;
+    int* st_host;
+    int seq;
+};
+__device__ __forceinline__ void mt_batch_end(const BatchEnd& e) {
+    if (mt_block_done(e.done)) mt_publish_status(e.st_host, e.seq, 0, (int)gridDim.x);
+}
+
+// The extractor's batch outputs as a batch matcher reads them: kps [image][cap] records, desc
+// [image][cap][32], counts [image][2] = {n, monoIndex}, uright [frame][cap] or nullptr. Frame f of the
+// call is image base + f * step; nmax: the most keypoints a workgroup of the call holds.
+struct SlabView {
+    const OrbKeyPoint* kps;
+    const uint8_t* desc;
+    const int* counts;
+    const float* uright;
+    int cap, base, step, nmax;
+    __device__ __forceinline__ int image(int f) const { return base + f * step; }
+    __device__ __forceinline__ int count(int img) const { return counts[2 * img]; }
+    __device__ __forceinline__ bool over(int N) const { return N < 0 || N > nmax; }
+    __device__ __forceinline__ const OrbKeyPoint* keys_of(int img) const { return kps + (size_t)img * cap; }
+    __device__ __forceinline__ const uint8_t* desc_of(int img) const { return desc + (size_t)img * cap * 32; }
+    // frame f (image img, N keypoints) of the call whose geometry is fr0
+    __device__ __forceinline__ FrameDev frame(const FrameDev& fr0, int f, int img, int N) const {
+        FrameDev fr = fr0;
+        fr.n = N;
+        fr.keys = keys_of(img);
+        fr.desc = (const uint32_t*)desc_of(img);
+        fr.uright = uright ? uright + (size_t)f * cap : nullptr;
+        return fr;
+    }
 };
 
 __device__ __forceinline__ int mt_hamming(const uint8_t* a, const uint32_t* b) {
@@ -1338,17 +1415,8 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_block(FrameDev fr, BlkGeom gm
     const int passes = blk_search<MODE>(fr, gm, QS, qid, qang, nq, nnratio, maxDist, need_obs, io, mt_sm,
                                         [&](int q) { return blk_load<MODE>(fr, rq, q, th, a0, a1, thFar); }, cnt);
     if (tid == 0) {
-        __threadfence_system();
         if (io.stats) io.stats[2] = (unsigned long long)passes;
-        volatile int* st = io.st_host;
-        st[0] = 0;
-        st[1] = cnt[0];
-        st[2] = cnt[1];
-        st[3] = passes;
-        st[5] = io.ntm ? *io.ntm : 0;
-        __threadfence_system();
-        st[4] = io.seq;
-        __threadfence_system();
+        mt_publish_status(io.st_host, io.seq, 0, cnt[0], cnt[1], passes, io.ntm ? *io.ntm : 0);
     }
 }
 
@@ -1564,17 +1632,8 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_block2(FrameDev fr, BlkGeom g
     __builtin_amdgcn_s_waitcnt(0);
     SYNC();
     if (tid == 0) {
-        __threadfence_system();
         if (io.stats) io.stats[2] = (unsigned long long)(pass + 1);
-        volatile int* st = io.st_host;
-        st[0] = 0;
-        st[1] = s_cnt[0];
-        st[2] = s_cnt[1];
-        st[3] = pass + 1;
-        st[5] = 0;
-        __threadfence_system();
-        st[4] = io.seq;
-        __threadfence_system();
+        mt_publish_status(io.st_host, io.seq, 0, s_cnt[0], s_cnt[1], pass + 1);
     }
 #ifdef ORBFE_BLK2_STAMPS
     BLK2_STAMP(5);
@@ -1806,17 +1865,8 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_block4(FrameDev fr, BlkGeom g
     __builtin_amdgcn_s_waitcnt(0);
     SYNC();
     if (tid == 0) {
-        __threadfence_system();
         if (io.stats) io.stats[2] = (unsigned long long)(pass + 1);
-        volatile int* st = io.st_host;
-        st[0] = aborted ? 2 : 0;
-        st[1] = s_cnt;
-        st[2] = 0;
-        st[3] = pass + 1;
-        st[5] = io.ntm ? *io.ntm : 0;
-        __threadfence_system();
-        st[4] = io.seq;
-        __threadfence_system();
+        mt_publish_status(io.st_host, io.seq, aborted ? 2 : 0, s_cnt, 0, pass + 1, io.ntm ? *io.ntm : 0);
     }
 }
 
@@ -1929,17 +1979,10 @@ __device__ void multi_pass_end(const MultiIO& io, const orbfe_map_point* recs, i
     SYNC();
     if (tid == 0) {
         if (conv || final_) {
-            __threadfence_system();
             if (io.stats) io.stats[2] = (unsigned long long)(p + 1);
-            volatile int* st = io.st_host;
-            st[0] = conv ? 0 : 1;
-            st[1] = __hip_atomic_load(&io.cnt[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            st[2] = 0;
-            st[3] = p + 1;
-            st[5] = io.ntm ? *io.ntm : 0;
-            __threadfence_system();
-            st[4] = io.seq;
-            __threadfence_system();
+            mt_publish_status(io.st_host, io.seq, conv ? 0 : 1,
+                              __hip_atomic_load(&io.cnt[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), 0, p + 1,
+                              io.ntm ? *io.ntm : 0);
         }
         __hip_atomic_store(&io.done[p], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(&io.cnt[p], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2601,17 +2644,15 @@ __device__ __forceinline__ BlkQuery kfb_query(const FrameDev& fr, const KfbCand&
 }
 // mvp_in / mvp_out: [n_kfs][fr.n] rows (device copy in, mapped pinned out: a row's untouched slots keep
 // the value the host put there). counts: [n_kfs][2] = {assigned, dropped} per candidate, mapped pinned.
-// done: zeroed by the call's upload; the workgroup that brings it to gridDim.x has seen every other
-// one's release, and publishes the sequence word as k_sbp_block's tail does.
+// end: the call's completion (mt_batch_end).
 struct KfbIn {
     const KfbCand* cands;
     const uint8_t* arena;
     const int32_t* mvp_in;
     int32_t* mvp_out;
     int* counts;
-    int* done;
-    int* st_host;
-    int seq, checkOri, maxDist;
+    BatchEnd end;
+    int checkOri, maxDist;
     float th;
 };
 __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_kf_batch(FrameDev fr, BlkGeom gm, KfbIn in) {
@@ -2648,21 +2689,7 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_kf_batch(FrameDev fr, BlkGeom
         volatile int* co = in.counts + 2 * c;
         co[0] = cnt ? cnt[0] : 0;
         co[1] = cnt ? cnt[1] : 0;
-        // this workgroup's rows and counts are released at system scope before it is counted
-        __threadfence_system();
-        const int before = __hip_atomic_fetch_add(in.done, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (before == (int)gridDim.x - 1) {
-            __threadfence_system();
-            volatile int* st = in.st_host;
-            st[0] = 0;
-            st[1] = (int)gridDim.x;
-            st[2] = 0;
-            st[3] = 0;
-            st[5] = 0;
-            __threadfence_system();
-            st[4] = in.seq;
-            __threadfence_system();
-        }
+        mt_batch_end(in.end);   // this workgroup's rows and counts are released before it is counted
     }
 }
 
@@ -2717,9 +2744,8 @@ __global__ __launch_bounds__(MT_NT) void k_mt_commit_drop(const OrbKeyPoint* key
 }
 
 // Status publication (st_host != nullptr): pinned host words {gate value, assigned count, dropped
-// count, passes needed, sequence number}; the last block to finish (done counter) stores them after
-// every block's slot writes, at system scope, the sequence number last, so a host that sees the
-// sequence number sees complete results. changed / npass: the pass change flags of this launch
+// count, passes needed, sequence number}; the last block to finish (done counter) publishes them
+// after every block's slot writes (mt_publish_status<4>). changed / npass: the pass change flags of this launch
 // batch (passes needed = first pass that changed nothing, + 1).
 struct CommitStatus {
     int* st_host;
@@ -2746,18 +2772,10 @@ __global__ void k_mt_commit_write(int n, const int* qid, int q_stride_bytes, con
     __syncthreads();
     if (threadIdx.x == 0) __threadfence_system();
     if (threadIdx.x == 0 && atomicAdd(cs.done, 1) == (int)gridDim.x - 1) {
-        __threadfence_system();
         int need = cs.npass;
         for (int p = 0; p < cs.npass; p++)
             if (cs.changed[p] == 0) { need = p + 1; break; }
-        volatile int* st = cs.st_host;
-        st[0] = g;
-        st[1] = result[0];
-        st[2] = result[1];
-        st[3] = need;
-        __threadfence_system();
-        st[4] = cs.seq;
-        __threadfence_system();
+        mt_publish_status<4>(cs.st_host, cs.seq, g, result[0], result[1], need);
         *cs.done = 0;   // every block has counted: ready for the next batch's commit
     }
 }
@@ -2968,15 +2986,7 @@ __global__ __launch_bounds__(1024) void k_init_commit(FrameDev f1, FrameDev f2, 
     // every wave's output stores complete, the barrier, one system-scope release, then the status
     __builtin_amdgcn_s_waitcnt(0);
     SYNC();
-    if (threadIdx.x == 0) {
-        __threadfence_system();
-        volatile int* st = st_host;
-        st[0] = run ? 0 : 1;
-        st[1] = run ? s_n : 0;
-        __threadfence_system();
-        st[4] = seq;
-        __threadfence_system();
-    }
+    if (threadIdx.x == 0) mt_publish_status<2>(st_host, seq, run ? 0 : 1, run ? s_n : 0);
 }
 
 // ---- SearchByBoW(KF, F) (ORBmatcher.cc:223-425): one thread per node present in both vectors.
@@ -3263,6 +3273,36 @@ __device__ __forceinline__ void bow_commit_rows(int n, const int* match, OwnAng 
     atomicAdd(s_n, cnt);
 }
 
+// SearchByBoW(KF, F) of one workgroup against a resident keyframe pack, once its arrays are in place
+// (wherever each of them lives: k_bow_batch and k_bow_slabs' LDS form stage them, the HBM form reads them
+// in place). One quad per KF node: the node finds its F node by binary search of F's node ids (the
+// reference's lower_bound walk gives the same pairs), bow_walk_node under BowRulesKfF walks it, and
+// bow_commit_rows<false> with AngFlat on the pack's angles commits the row. src is filled with -1, s_hist
+// zeroed, s_n 0, and a barrier has passed. On return s_n holds nmatches and a barrier has passed.
+__device__ __forceinline__ void bow_join_match(const unsigned* knid, const int* kfo, const int* kfi, const float* kang,
+                                               const uint4* kd, const int* mp, int nn, const unsigned* s_fnid,
+                                               const int* s_fo, const int* fi, const uint4* fd, int* s_src, int fvn,
+                                               int n, int nleft, const float (&fang)[MT_BOW_FR], float nnratio,
+                                               int checkOri, int* out, int* s_hist, unsigned* s_keep, int* s_n) {
+    const int tid = threadIdx.x;
+    const BowRulesKfF rules{mp, s_src, nleft, nnratio};
+    for (int a = tid >> 2; a < nn; a += MT_BOW_NT / 4) {
+        const unsigned id = knid[a];
+        int b = 0, hi = fvn;   // lower_bound of the node id among F's (the quad's lanes agree)
+        while (b < hi) {
+            const int mid = (b + hi) >> 1;
+            if (s_fnid[mid] < id) b = mid + 1;
+            else hi = mid;
+        }
+        if (b >= fvn || s_fnid[b] != id) continue;
+        bow_walk_node(kfo[a], kfo[a + 1], s_fo[b], s_fo[b + 1], kfi, fi, kd, fd, tid & 3, rules);
+    }
+    SYNC();
+    bow_commit_rows<false>(n, s_src, [&](int u, int) { return fang[u]; }, AngFlat{kang}, mp, checkOri, out, s_hist,
+                           s_keep, s_n);
+    SYNC();
+}
+
 // SearchByBoW(KF, F) in ONE workgroup (the Tracking thread's TrackReferenceKeyFrame / Relocalization
 // calls, Tracking.cc:2836,3765): both descriptor sets, the node lists and the match state in LDS, one
 // quad per entry of the host's node-pair list (bow_walk_node under BowRulesKfF), the commit in the same
@@ -3332,19 +3372,12 @@ __global__ __launch_bounds__(MT_BOW_NT) void k_bow_block(BowBlockIn in, int* out
     // F's angles were loaded at the start
     bow_commit_rows<false>(in.fn, s_src, [&](int u, int) { return fang[u]; }, AngKeys{s_kk}, s_mp, in.checkOri, out,
                            s_hist, &s_keep, &s_n);
-    // every wave's output stores complete (vmcnt 0), the barrier, then one system-scope release before
-    // the status words the host waits for (as k_sbp_block)
+    // every wave's output stores complete (vmcnt 0), the barrier, then the hand-off (mt_publish_status)
     __builtin_amdgcn_s_waitcnt(0);
     SYNC();
     if (tid == 0) {
         result[0] = s_n;
-        __threadfence_system();
-        volatile int* st = in.st_host;
-        st[0] = 0;
-        st[1] = s_n;
-        __threadfence_system();
-        st[4] = in.seq;
-        __threadfence_system();
+        mt_publish_status<2>(in.st_host, in.seq, 0, s_n);
     }
 #ifdef ORBFE_BOW_STAMPS
     BOW_STAMP(3);
@@ -3427,32 +3460,12 @@ __global__ __launch_bounds__(MT_BOW_NT) void k_bow_batch(BowBatchIn in) {
     if (tid < MT_HISTO) s_hist[tid] = 0;
     if (tid == 0) s_n = 0;
     SYNC();
-    const unsigned* s_fnid = (const unsigned*)s_fm;
-    const int* s_fo = (const int*)((const uint8_t*)s_fm + in.o_foff);
-    const int* s_fi = (const int*)((const uint8_t*)s_fm + in.o_fidx);
-    const unsigned* s_knid = (const unsigned*)s_kf;
-    const int* s_kfo = (const int*)((const uint8_t*)s_kf + cd.o_off);
-    const int* s_kfi = (const int*)((const uint8_t*)s_kf + cd.o_idx);
-    const float* s_ang = (const float*)((const uint8_t*)s_kf + cd.o_ang);
-    const uint4* s_kd = (const uint4*)((const uint8_t*)s_kf + cd.o_desc);
-    const uint4* s_fd = s_fdw;
-    const int* s_mp = (const int*)s_mpw;
-    const BowRulesKfF rules{s_mp, s_src, in.nleft, in.nnratio};
-    for (int a = tid >> 2; a < cd.nn; a += MT_BOW_NT / 4) {   // one quad per KF node
-        const unsigned id = s_knid[a];
-        int b = 0, hi = in.fnn;   // lower_bound of the node id among F's (the quad's lanes agree)
-        while (b < hi) {
-            const int mid = (b + hi) >> 1;
-            if (s_fnid[mid] < id) b = mid + 1;
-            else hi = mid;
-        }
-        if (b >= in.fnn || s_fnid[b] != id) continue;
-        bow_walk_node(s_kfo[a], s_kfo[a + 1], s_fo[b], s_fo[b + 1], s_kfi, s_fi, s_kd, s_fd, tid & 3, rules);
-    }
-    SYNC();
-    bow_commit_rows<false>(in.fn, s_src, [&](int u, int) { return fang[u]; }, AngFlat{s_ang}, s_mp, in.checkOri, out,
-                           s_hist, &s_keep, &s_n);
-    SYNC();
+    const uint8_t* fm = (const uint8_t*)s_fm;
+    const uint8_t* sk = (const uint8_t*)s_kf;
+    bow_join_match((const unsigned*)sk, (const int*)(sk + cd.o_off), (const int*)(sk + cd.o_idx),
+                   (const float*)(sk + cd.o_ang), (const uint4*)(sk + cd.o_desc), (const int*)s_mpw, cd.nn,
+                   (const unsigned*)fm, (const int*)(fm + in.o_foff), (const int*)(fm + in.o_fidx), s_fdw, s_src,
+                   in.fnn, in.fn, in.nleft, fang, in.nnratio, in.checkOri, out, s_hist, &s_keep, &s_n);
     if (tid == 0) in.nm[c] = s_n;   // the host reads the rows after a stream synchronisation
 }
 // the angles of a device-resident keyframe's keypoints, gathered into its pack at create
@@ -3570,10 +3583,9 @@ __global__ __launch_bounds__(64 * W) void k_knn2_batch(StereoSide SL, StereoSide
 // =============================================================================================
 namespace {
 
-// The zero-copy status words: a commit kernel stores the slots and st[0..3,5], fences at system
-// scope, then stores the sequence word st[4]. The host spin reads st[4] with ACQUIRE semantics, so
-// neither the compiler nor the CPU may move the later reads of the slots (memcpy from the mapped
-// block) or of st[0..5] above the read that saw the new sequence number.
+// The zero-copy status words, host side of mt_publish_status: the host spin reads st[4] with ACQUIRE
+// semantics, so neither the compiler nor the CPU may move the later reads of the slots (memcpy from the
+// mapped block) or of st[0..5] above the read that saw the new sequence number.
 inline int host_seq_acquire(volatile int* st) { return __atomic_load_n((int*)&st[4], __ATOMIC_ACQUIRE); }
 
 struct MatchScratch {
@@ -3771,6 +3783,93 @@ inline int ms_out_block(size_t words, size_t grow_to) {
     m.ocap = grow_to;
     return ORBFE_OK;
 }
+// the batch calls' sizing of it: nout words (the rows, then the per-job counts), grown by half
+inline int ms_out_rows(size_t nout) { return ms_out_block(nout, std::max<size_t>(nout + nout / 2, 2048)); }
+
+// ---- the one-launch batch calls' shared scaffold (the calls over the extractor's slabs and
+// orbfe_search_by_projection_kf_batch). Each driver stays a straight line over these. ----
+// The slabs' own refusals (ORBFE_E_ARG) and the bound on a call's rows (ORBFE_E_CAPACITY)
+inline bool slabs_ok(const void* kps, const void* desc, const void* counts, int cap, int base, int step) {
+    return kps && desc && counts && cap > 0 && base >= 0 && step >= 0;
+}
+inline bool slab_rows_ok(int nrows, int cap) { return (size_t)nrows * (size_t)cap <= ((size_t)1 << 26); }
+// A batch call's completion (BatchEnd, mt_batch_end): the zeroed counter is planned with the call's
+// uploads; ms_batch_prepare is ms_prepare, the out block for nout words and the call's sequence number.
+inline size_t ms_plan_done(Plan& p) {
+    static const int zero = 0;
+    return p.upload(&zero, 4);
+}
+inline int ms_batch_prepare(const Plan& p, size_t nout, size_t o_done, BatchEnd& e) {
+    MSCHK(ms_prepare(p));
+    MSCHK(ms_out_rows(nout));
+    e = BatchEnd{ms_ptr<int>(o_done), t_ms.hs_dev, ++t_ms.seq};
+    return ORBFE_OK;
+}
+// Each distinct (array, tag) of a call uploaded once: jobs that name the same one share its offset
+struct UploadOnce {
+    std::map<std::pair<const void*, uintptr_t>, size_t> seen;
+    size_t operator()(Plan& p, const void* src, uintptr_t tag, size_t bytes) {
+        auto it = seen.find({src, tag});
+        if (it == seen.end()) it = seen.emplace(std::make_pair(src, tag), p.upload(src, bytes)).first;
+        return it->second;
+    }
+};
+// The slabs were written on the caller's stream: the thread's matcher stream waits for an event recorded
+// there (one event per thread and device). After ms_prepare.
+thread_local hipEvent_t t_track_ev = nullptr;
+thread_local int t_track_ev_dev = -1;
+inline int ms_after_caller(void* caller) {
+    if (t_track_ev_dev != t_ms.device) {
+        HIPCHK(hipEventCreateWithFlags(&t_track_ev, hipEventDisableTiming));
+        t_track_ev_dev = t_ms.device;
+    }
+    HIPCHK(hipEventRecord(t_track_ev, (hipStream_t)caller));
+    HIPCHK(hipStreamWaitEvent(t_ms.stream, t_track_ev, 0));
+    return ORBFE_OK;
+}
+// The FrameDev every frame of a slab call starts from (SlabView::frame fills in the rest): geom's bounds
+// and levels, the uploaded scale factors. After ms_prepare.
+inline FrameDev ms_geom_frame(const orbfe_frame* geom, size_t o_scale) {
+    FrameDev fr;
+    memset(&fr, 0, sizeof(fr));
+    fr.minx = geom->min_x; fr.maxx = geom->max_x; fr.miny = geom->min_y; fr.maxy = geom->max_y;
+    fr.invw = static_cast<float>(ORBFE_GRID_COLS) / (geom->max_x - geom->min_x);
+    fr.invh = static_cast<float>(ORBFE_GRID_ROWS) / (geom->max_y - geom->min_y);
+    fr.mbf = geom->mbf;
+    fr.nlevels = geom->nlevels;
+    fr.scale = ms_ptr<const float>(o_scale);
+    fr.nleft = -1;
+    return fr;
+}
+// mpCamera as the kernels read it: `model` when given (cam_model_ok), else the pinhole (fx, fy, cx, cy)
+inline bool cam_model_ok(const orbfe_camera_model* m) {
+    return m->type == ORBFE_CAM_PINHOLE || m->type == ORBFE_CAM_KANNALA_BRANDT8;
+}
+inline CamModelDev make_cam_model(const orbfe_camera_model* model, float fx = 0.f, float fy = 0.f, float cx = 0.f,
+                                  float cy = 0.f) {
+    CamModelDev o;
+    memset(&o, 0, sizeof(o));
+    o.type = model ? model->type : ORBFE_CAM_PINHOLE;
+    o.fx = model ? model->params[0] : fx;
+    o.fy = model ? model->params[1] : fy;
+    o.cx = model ? model->params[2] : cx;
+    o.cy = model ? model->params[3] : cy;
+    if (o.type == ORBFE_CAM_KANNALA_BRANDT8)
+        for (int k = 0; k < 4; k++) o.k[k] = model->params[4 + k];
+    return o;
+}
+// Per-device opt-in of KERNEL to `bytes` of dynamic LDS, made once per device before the first launch
+// that asks for more than 64 KB (`lds`). Each kernel's instantiation keeps its own devices-set mask.
+template <auto KERNEL>
+inline int ms_lds_optin(int device, size_t lds, size_t bytes) {
+    static std::atomic<unsigned long long> set{0};
+    if (lds <= 64 * 1024 || device < 0 || device >= 64 || (set.load(std::memory_order_acquire) >> device & 1ull))
+        return ORBFE_OK;
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)bytes));
+    set.fetch_or(1ull << device, std::memory_order_release);
+    return ORBFE_OK;
+}
 
 // One device int through the pinned status words (a pageable 4-byte read back costs more than the
 // kernels it follows). Copies queued on s before it complete under the same synchronisation.
@@ -3955,22 +4054,12 @@ bool make_camdev(const orbfe_frame* F, const orbfe_camera* cam, const orbfe_ster
     cd.minx = F->min_x; cd.maxx = F->max_x; cd.miny = F->min_y; cd.maxy = F->max_y;
     cd.mbf = F->mbf;
     cd.nlevels = F->nlevels;
-    auto model = [](const orbfe_camera_model& m, CamModelDev& o) {
-        if (m.type != ORBFE_CAM_PINHOLE && m.type != ORBFE_CAM_KANNALA_BRANDT8) return false;
-        o.type = m.type;
-        o.fx = m.params[0]; o.fy = m.params[1]; o.cx = m.params[2]; o.cy = m.params[3];
-        for (int k = 0; k < 4; k++) o.k[k] = m.type == ORBFE_CAM_KANNALA_BRANDT8 ? m.params[4 + k] : 0.f;
-        return true;
-    };
-    if (rig) {
-        if (!model(rig->left, cd.cl)) return false;
-    } else {
-        cd.cl.type = ORBFE_CAM_PINHOLE;
-        cd.cl.fx = cam->fx; cd.cl.fy = cam->fy; cd.cl.cx = cam->cx; cd.cl.cy = cam->cy;
-    }
+    if (rig && !cam_model_ok(&rig->left)) return false;
+    cd.cl = make_cam_model(rig ? &rig->left : nullptr, cam->fx, cam->fy, cam->cx, cam->cy);
     cd.two = F->two_cams ? 1 : 0;
     if (cd.two) {
-        if (!model(rig->right, cd.cr)) return false;
+        if (!cam_model_ok(&rig->right)) return false;
+        cd.cr = make_cam_model(&rig->right);
         const float* A = rig->Rrl;
         for (int i = 0; i < 3; i++) {
             for (int j = 0; j < 3; j++)   // mR = Rrl * mRcw
@@ -4681,7 +4770,7 @@ int orbfe_search_by_projection_lastframe_pose(const orbfe_frame* cur, int32_t* m
     if (!cur || !Tcw || !cam || n_pts < 0 || (n_pts > 0 && !pts)) return ORBFE_E_ARG;
     const bool two = cur->two_cams != 0;
     if (two && !Trl) return ORBFE_E_ARG;
-    if (cam->type != ORBFE_CAM_PINHOLE && cam->type != ORBFE_CAM_KANNALA_BRANDT8) return ORBFE_E_ARG;
+    if (!cam_model_ok(cam)) return ORBFE_E_ARG;
     // nLastOctave addresses mvScaleFactors (as the host-projected entry points check)
     for (int j = 0; j < n_pts; j++)
         if (pts[j].valid && (pts[j].octave < 0 || pts[j].octave >= cur->nlevels)) return ORBFE_E_ARG;
@@ -4695,9 +4784,7 @@ int orbfe_search_by_projection_lastframe_pose(const orbfe_frame* cur, int32_t* m
         lp.Trl.kind = ORBFE_SE3;
     }
     lp.two = two ? 1 : 0;
-    lp.cam.type = cam->type;
-    lp.cam.fx = cam->params[0]; lp.cam.fy = cam->params[1]; lp.cam.cx = cam->params[2]; lp.cam.cy = cam->params[3];
-    for (int k = 0; k < 4; k++) lp.cam.k[k] = cam->type == ORBFE_CAM_KANNALA_BRANDT8 ? cam->params[4 + k] : 0.f;
+    lp.cam = make_cam_model(cam);
     return sbp_run(1, cur, mvp, mvp_obs, nullptr, n_pts, kProjPointRec, th, bForward, bBackward, 0.f, 0.f, MT_TH_HIGH,
                    checkOri, nullptr, nullptr, nullptr, &lp);
 }
@@ -4726,7 +4813,7 @@ int orbfe_search_by_projection_kf_batch(const orbfe_frame* cur, const orbfe_keyf
     orbfe_frame Fchk = *cur;
     Fchk.device = 0;   // a device view's arrays are checked for presence only
     if (!frame_ok(&Fchk) || cur->two_cams) return ORBFE_E_ARG;
-    if (model && model->type != ORBFE_CAM_PINHOLE && model->type != ORBFE_CAM_KANNALA_BRANDT8) return ORBFE_E_ARG;
+    if (model && !cam_model_ok(model)) return ORBFE_E_ARG;
     const int n = cur->n;
     bool any = false;
     for (int c = 0; c < n_kfs; c++) {
@@ -4740,7 +4827,7 @@ int orbfe_search_by_projection_kf_batch(const orbfe_frame* cur, const orbfe_keyf
         if (n_pts[c] > MT_BLOCK_MAXQ) return ORBFE_E_CAPACITY;
     BlkGeom gm;
     if (n > 0 && !blk_geom(cur, gm)) return ORBFE_E_CAPACITY;
-    if ((size_t)n_kfs * (size_t)std::max(n, 1) > ((size_t)1 << 26)) return ORBFE_E_CAPACITY;
+    if (!slab_rows_ok(n_kfs, std::max(n, 1))) return ORBFE_E_CAPACITY;
     for (int c = 0; c < n_kfs; c++) {   // KF slots: strictly ascending, inside the keyframe
         if (!kfs[c]) continue;
         int prev = -1;
@@ -4773,8 +4860,7 @@ int orbfe_search_by_projection_kf_batch(const orbfe_frame* cur, const orbfe_keyf
     const size_t o_mvp = p.upload(mvp, (size_t)n_kfs * n * 4);
     std::vector<KfbCand> cands(n_kfs);
     const size_t o_cands = p.upload(cands.data(), (size_t)n_kfs * sizeof(KfbCand));   // filled below, copied by ms_prepare
-    const int zero = 0;
-    const size_t o_done = p.upload(&zero, 4);
+    const size_t o_done = ms_plan_done(p);
     for (int c = 0; c < n_kfs; c++) {
         KfbCand& cd = cands[c];
         memset(&cd, 0, sizeof(cd));
@@ -4787,31 +4873,23 @@ int orbfe_search_by_projection_kf_batch(const orbfe_frame* cur, const orbfe_keyf
         cd.T = cams[c].Tcw;
         cd.T.kind = ORBFE_SE3;
         memcpy(cd.Ow, cams[c].Ow, sizeof(cd.Ow));
-        cd.cam.type = model ? model->type : ORBFE_CAM_PINHOLE;
-        cd.cam.fx = model ? model->params[0] : cams[c].fx;
-        cd.cam.fy = model ? model->params[1] : cams[c].fy;
-        cd.cam.cx = model ? model->params[2] : cams[c].cx;
-        cd.cam.cy = model ? model->params[3] : cams[c].cy;
-        for (int k = 0; k < 4; k++)
-            cd.cam.k[k] = (model && model->type == ORBFE_CAM_KANNALA_BRANDT8) ? model->params[4 + k] : 0.f;
+        cd.cam = make_cam_model(model, cams[c].fx, cams[c].fy, cams[c].cx, cams[c].cy);
     }
-    MSCHK(ms_prepare(p));
     const size_t nrow = (size_t)n_kfs * n, nout = nrow + 2 * (size_t)n_kfs;   // the rows, then {assigned, dropped}
-    MSCHK(ms_out_block(nout, std::max<size_t>(nout + nout / 2, 2048)));
+    BatchEnd end;
+    MSCHK(ms_batch_prepare(p, nout, o_done, end));
     MatchScratch& m = t_ms;
     hipStream_t s = m.stream;
     MsTimer timer(s);
     const FrameDev fr = fp.view();
-    const int seq = ++t_ms.seq;
     memcpy(m.ho, mvp, nrow * 4);   // the slots the search leaves alone keep their value
     const KfbIn in{ms_ptr<const KfbCand>(o_cands), ms_ptr<const uint8_t>(0), ms_ptr<const int32_t>(o_mvp), m.ho_dev,
-                   m.ho_dev + nrow,
-                   ms_ptr<int>(o_done), t_ms.hs_dev, seq, checkOri ? 1 : 0, ORBdist, th};
+                   m.ho_dev + nrow, end, checkOri ? 1 : 0, ORBdist, th};
     // one workgroup per candidate, each with k_sbp_block's LDS frame
     hipLaunchKernelGGL(k_sbp_kf_batch, dim3(n_kfs), dim3(MT_BLK_NT), blk_lds(n, cur->nlevels, gm), s, fr, gm, in);
     HIPCHK(hipGetLastError());
     timer.end();
-    MSCHK(ms_wait_seq(s, seq));
+    MSCHK(ms_wait_seq(s, end.seq));
     memcpy(mvp, m.ho, nrow * 4);   // complete: the sequence word comes after every workgroup's release
     for (int c = 0; c < n_kfs; c++) nmatches[c] = m.ho[nrow + 2 * c] - m.ho[nrow + 2 * c + 1];
     return ORBFE_OK;
@@ -5167,7 +5245,7 @@ int orbfe_search_by_bow_batch(const orbfe_keyframe* const* kfs, const int32_t* c
     int rc = ms_prepare(p);
     if (rc) return rc;
     const size_t nout = (size_t)n_kfs * fn + (size_t)n_kfs;   // the rows, then nmatches
-    MSCHK(ms_out_block(nout, std::max<size_t>(nout + nout / 2, 2048)));
+    MSCHK(ms_out_rows(nout));
     MatchScratch& m = t_ms;
     MsTimer timer;
     hipStream_t s = m.stream;

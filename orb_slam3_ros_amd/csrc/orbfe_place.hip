@@ -192,7 +192,7 @@ int orbfe_search_by_bow_kf_batch(const orbfe_keyframe* kf1, const int32_t* mp1, 
     int rc = ms_prepare(p);
     if (rc) return rc;
     const size_t nout = (size_t)n_kfs * n1 + (size_t)n_kfs;   // the rows, then nmatches
-    MSCHK(ms_out_block(nout, std::max<size_t>(nout + nout / 2, 2048)));
+    MSCHK(ms_out_rows(nout));
     MatchScratch& m = t_ms;
     MsTimer timer;
     hipStream_t s = m.stream;

@@ -58,48 +58,37 @@ __device__ __forceinline__ BlkQuery trk_query(const FrameDev& fr, const TrkJob& 
     memcpy(Q.qd, p.desc, 32);
     return Q;
 }
-// kps / desc / counts: the extractor's batch outputs ([image][cap] records, [image][cap][32],
-// [image][2] = {n, monoIndex}); uright: [nframes][cap] or nullptr. rows: [nframes][cap] slots in HBM
-// (the search's mvp_in and mvp_out: filled with -1 here, so every slot is free); mvp_out: the same rows
-// in mapped pinned memory, each slot stored once, after the search. counts_out: [nframes][3] =
-// {assigned (ORBFE_E_CAPACITY: a frame of more keypoints than the workgroup holds), dropped, N}.
-// done / st_host / seq: k_sbp_kf_batch's completion counter and sequence word.
+// sl: the extractor's batch outputs. rows: [nframes][cap] slots in HBM (the search's mvp_in and mvp_out:
+// filled with -1 here, so every slot is free); mvp_out: the same rows in mapped pinned memory, each slot
+// stored once, after the search. counts_out: [nframes][3] = {assigned (ORBFE_E_CAPACITY: a frame of more
+// keypoints than the workgroup holds), dropped, N}. end: the call's completion (mt_batch_end).
 struct TrkIn {
-    const OrbKeyPoint* kps;
-    const uint8_t* desc;
-    const int* counts;
-    const float* uright;
-    int cap, base, step, nmax;
+    SlabView sl;
     const TrkJob* jobs;
     const uint8_t* arena;
     int32_t* rows;
     int32_t* mvp_out;
     int* counts_out;
-    int* done;
-    int* st_host;
-    int seq, checkOri;
+    BatchEnd end;
+    int checkOri;
     CamModelDev cam;
 };
 __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_track_batch(FrameDev fr0, BlkGeom gm, TrkIn in) {
     extern __shared__ __attribute__((aligned(16))) uint8_t mt_sm[];
     const int tid = threadIdx.x, f = blockIdx.x;
-    const int img = in.base + f * in.step;
-    const int N = in.counts[2 * img];   // (uniform over the workgroup)
+    const int cap = in.sl.cap, img = in.sl.image(f);
+    const int N = in.sl.count(img);   // (uniform over the workgroup)
     const TrkJob& jb = in.jobs[f];
     const int nq = jb.nq;
-    int32_t* row = in.rows + (size_t)f * in.cap;
-    for (int k = tid; k < in.cap; k += MT_BLK_NT) row[k] = -1;
-    const bool over = N < 0 || N > in.nmax;
+    int32_t* row = in.rows + (size_t)f * cap;
+    for (int k = tid; k < cap; k += MT_BLK_NT) row[k] = -1;
+    const bool over = in.sl.over(N);
     const int* cnt = nullptr;
     if (nq > 0 && N > 0 && !over) {
         // the -1 fill is the staging's slot state: complete before any thread reads it
         __builtin_amdgcn_s_waitcnt(0);
         SYNC();
-        FrameDev fr = fr0;
-        fr.n = N;
-        fr.keys = in.kps + (size_t)img * in.cap;
-        fr.desc = (const uint32_t*)(in.desc + (size_t)img * in.cap * 32);
-        fr.uright = in.uright ? in.uright + (size_t)f * in.cap : nullptr;
+        const FrameDev fr = in.sl.frame(fr0, f, img, N);
         const orbfe_last_point* pts = (const orbfe_last_point*)(in.arena + jb.o_pts);
         int qid[MT_BLK_QPT];
         float qang[MT_BLK_QPT];
@@ -124,8 +113,8 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_track_batch(FrameDev fr0, Blk
         SYNC();
     }
     // the row to the host, each slot once (blk_search ended with its stores complete and a barrier)
-    int32_t* out = in.mvp_out + (size_t)f * in.cap;
-    for (int k = tid; k < in.cap; k += MT_BLK_NT) out[k] = row[k];
+    int32_t* out = in.mvp_out + (size_t)f * cap;
+    for (int k = tid; k < cap; k += MT_BLK_NT) out[k] = row[k];
     __builtin_amdgcn_s_waitcnt(0);
     SYNC();
     if (tid == 0) {
@@ -133,30 +122,13 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_track_batch(FrameDev fr0, Blk
         co[0] = over && nq > 0 ? ORBFE_E_CAPACITY : cnt ? cnt[0] : 0;
         co[1] = cnt ? cnt[1] : 0;
         co[2] = N;
-        // this workgroup's row and counts are released at system scope before it is counted
-        __threadfence_system();
-        const int before = __hip_atomic_fetch_add(in.done, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (before == (int)gridDim.x - 1) {
-            __threadfence_system();
-            volatile int* st = in.st_host;
-            st[0] = 0;
-            st[1] = (int)gridDim.x;
-            st[2] = 0;
-            st[3] = 0;
-            st[5] = 0;
-            __threadfence_system();
-            st[4] = in.seq;
-            __threadfence_system();
-        }
+        mt_batch_end(in.end);   // this workgroup's row and counts are released before it is counted
     }
 }
 
 namespace {
 // orbfe_matcher_last_track_batch: frames searched, skipped, over capacity (host record)
 thread_local int t_track_batch[3] = {0, 0, 0};
-// the event that orders the thread's matcher stream after the caller's (one per thread and device)
-thread_local hipEvent_t t_track_ev = nullptr;
-thread_local int t_track_ev_dev = -1;
 }  // namespace
 
 extern "C" {
@@ -171,11 +143,11 @@ int orbfe_search_by_projection_lastframe_slabs(const orbfe_keypoint* d_kps, cons
     // every refusal below comes before any device work and before any write to the outputs
     if (nframes < 0) return ORBFE_E_ARG;
     if (nframes == 0) return ORBFE_OK;
-    if (!d_kps || !d_desc || !d_counts || !geom || !cam || !jobs || !mvp_out || !nmatches || !n_keys)
+    if (!slabs_ok(d_kps, d_desc, d_counts, cap, base, step) || !geom || !cam || !jobs || !mvp_out || !nmatches ||
+        !n_keys)
         return ORBFE_E_ARG;
-    if (cap <= 0 || base < 0 || step < 0) return ORBFE_E_ARG;
     if (geom->two_cams || geom->nlevels <= 0 || !geom->scale_factors) return ORBFE_E_ARG;
-    if (cam->type != ORBFE_CAM_PINHOLE && cam->type != ORBFE_CAM_KANNALA_BRANDT8) return ORBFE_E_ARG;
+    if (!cam_model_ok(cam)) return ORBFE_E_ARG;
     for (int f = 0; f < nframes; f++) {
         const orbfe_track_job& j = jobs[f];
         if (j.n_pts < 0 || (j.n_pts > 0 && !j.pts) || j.Tcw.kind != ORBFE_SE3) return ORBFE_E_ARG;
@@ -194,7 +166,7 @@ int orbfe_search_by_projection_lastframe_slabs(const orbfe_keypoint* d_kps, cons
     G.n = nmax;
     BlkGeom gm;
     if (!blk_geom(&G, gm)) return ORBFE_E_CAPACITY;
-    if ((size_t)nframes * (size_t)cap > ((size_t)1 << 26)) return ORBFE_E_CAPACITY;
+    if (!slab_rows_ok(nframes, cap)) return ORBFE_E_CAPACITY;
     // one upload for the call: the scale factors, every job's points, the job table and the zeroed
     // completion counter
     Plan p;
@@ -211,56 +183,31 @@ int orbfe_search_by_projection_lastframe_slabs(const orbfe_keypoint* d_kps, cons
         if (t.nq > 0) t.o_pts = p.upload(jobs[f].pts, (size_t)t.nq * sizeof(orbfe_last_point));
     }
     const size_t o_jobs = p.upload(tj.data(), (size_t)nframes * sizeof(TrkJob));
-    const int zero = 0;
-    const size_t o_done = p.upload(&zero, 4);
+    const size_t o_done = ms_plan_done(p);
     const size_t nrow = (size_t)nframes * cap, nout = nrow + 3 * (size_t)nframes;   // the rows, then the counts
     const size_t o_rows = p.scratch(nrow * 4);
-    MSCHK(ms_prepare(p));
-    MSCHK(ms_out_block(nout, std::max<size_t>(nout + nout / 2, 2048)));
-    MatchScratch& m = t_ms;
-    hipStream_t s = m.stream;
-    // the slabs were written on the caller's stream: the launch waits for an event recorded there
-    if (t_track_ev_dev != m.device) {
-        HIPCHK(hipEventCreateWithFlags(&t_track_ev, hipEventDisableTiming));
-        t_track_ev_dev = m.device;
-    }
-    HIPCHK(hipEventRecord(t_track_ev, (hipStream_t)stream));
-    HIPCHK(hipStreamWaitEvent(s, t_track_ev, 0));
-    MsTimer timer(s);
-    FrameDev fr;
-    memset(&fr, 0, sizeof(fr));
-    fr.minx = geom->min_x; fr.maxx = geom->max_x; fr.miny = geom->min_y; fr.maxy = geom->max_y;
-    fr.invw = static_cast<float>(ORBFE_GRID_COLS) / (geom->max_x - geom->min_x);
-    fr.invh = static_cast<float>(ORBFE_GRID_ROWS) / (geom->max_y - geom->min_y);
-    fr.mbf = geom->mbf;
-    fr.nlevels = geom->nlevels;
-    fr.scale = ms_ptr<const float>(o_scale);
-    fr.nleft = -1;
     TrkIn in;
     memset(&in, 0, sizeof(in));
-    in.kps = (const OrbKeyPoint*)d_kps;
-    in.desc = d_desc;
-    in.counts = d_counts;
-    in.uright = d_uright;
-    in.cap = cap; in.base = base; in.step = step; in.nmax = nmax;
+    MSCHK(ms_batch_prepare(p, nout, o_done, in.end));
+    MatchScratch& m = t_ms;
+    hipStream_t s = m.stream;
+    MSCHK(ms_after_caller(stream));
+    MsTimer timer(s);
+    const FrameDev fr = ms_geom_frame(geom, o_scale);
+    in.sl = SlabView{(const OrbKeyPoint*)d_kps, d_desc, d_counts, d_uright, cap, base, step, nmax};
     in.jobs = ms_ptr<const TrkJob>(o_jobs);
     in.arena = ms_ptr<const uint8_t>(0);
     in.rows = ms_ptr<int32_t>(o_rows);
     in.mvp_out = m.ho_dev;
     in.counts_out = m.ho_dev + nrow;
-    in.done = ms_ptr<int>(o_done);
-    in.st_host = m.hs_dev;
-    in.seq = ++m.seq;
     in.checkOri = checkOri ? 1 : 0;
-    in.cam.type = cam->type;
-    in.cam.fx = cam->params[0]; in.cam.fy = cam->params[1]; in.cam.cx = cam->params[2]; in.cam.cy = cam->params[3];
-    for (int k = 0; k < 4; k++) in.cam.k[k] = cam->type == ORBFE_CAM_KANNALA_BRANDT8 ? cam->params[4 + k] : 0.f;
+    in.cam = make_cam_model(cam);
     // one workgroup per frame, each with k_sbp_block's LDS frame for nmax keypoints
     hipLaunchKernelGGL(k_sbp_track_batch, dim3(nframes), dim3(MT_BLK_NT), blk_lds(nmax, geom->nlevels, gm), s, fr, gm,
                        in);
     HIPCHK(hipGetLastError());
     timer.end();
-    MSCHK(ms_wait_seq(s, in.seq));
+    MSCHK(ms_wait_seq(s, in.end.seq));
     memcpy(mvp_out, m.ho, nrow * 4);   // complete: the sequence word comes after every workgroup's release
     for (int f = 0; f < nframes; f++) {
         const int* co = m.ho + nrow + 3 * (size_t)f;
