@@ -406,6 +406,21 @@ int orbfe_keyframe_create(const orbfe_frame* KF, const orbfe_feature_vector* fv,
 void orbfe_keyframe_destroy(orbfe_keyframe* kf);
 int orbfe_keyframe_n(const orbfe_keyframe* kf);
 
+/* A resident keyframe with geometry: everything orbfe_keyframe_create keeps (the same pack, so the
+ * handle is valid wherever a handle is accepted), and in a second device block what
+ * SearchForTriangulation reads besides: per keypoint x, y, octave and mvuRight (all -1, "not stereo",
+ * when KF->uright is NULL or KF->two_cams is set, as orbfe_search_for_triangulation reads them), and per
+ * keyframe nlevels, mvScaleFactors (KF->scale_factors), mvLevelSigma2 (level_sigma2 [nlevels], always
+ * host memory) and the two_cams flag. Reads KF->n, keys, desc, uright, nlevels, scale_factors, two_cams
+ * and device; with KF->device == 1 keys / desc / uright / scale_factors are device pointers.
+ * ORBFE_E_ARG, before any allocation: what orbfe_keyframe_create refuses, nlevels < 1, a NULL
+ * scale_factors or level_sigma2, a keypoint octave outside [0, nlevels) on a host view (a device view's
+ * octaves cannot be read here and are clamped to the level tables).
+ * orbfe_keyframe_has_geom: 1 for such a handle, 0 for one of orbfe_keyframe_create, ORBFE_E_ARG for NULL. */
+int orbfe_keyframe_create_geom(const orbfe_frame* KF, const orbfe_feature_vector* fv, const float* level_sigma2,
+                               orbfe_keyframe** out);
+int orbfe_keyframe_has_geom(const orbfe_keyframe* kf);
+
 /* SearchByBoW(kfs[c], F, out[c]) for c in [0, n_kfs) in one call and one kernel launch, one workgroup
  * per candidate. kfs[c] == NULL is a discarded candidate (pKF->isBad()): its row is all -1 and
  * nmatches[c] = 0. kf_mp[c]: [orbfe_keyframe_n(kfs[c])] map-point handles with bad / NULL points as
@@ -617,6 +632,37 @@ int orbfe_search_for_triangulation(const orbfe_frame* KF1, const int32_t* mp1, c
                                    const orbfe_frame* KF2, const int32_t* mp2, const orbfe_feature_vector* fv2,
                                    const float* F12, const float* ep, const float* level_sigma2_2,
                                    int32_t bOnlyStereo, int32_t bCoarse, int32_t checkOri, int32_t* matches12);
+
+/* One covisible neighbour of orbfe_search_for_triangulation_batch. 64 bytes. */
+typedef struct orbfe_tri_job {
+    const orbfe_keyframe* kf2;       /* resident, with geometry; NULL: the neighbour is skipped (the baseline
+                                        gate, isBad()): its row is all -1 and nmatches 0 */
+    const int32_t* mp2;              /* [orbfe_keyframe_n(kf2)] GetMapPoint(idx) presence, host memory: the
+                                        only per-neighbour upload (ignored for NULL kf2) */
+    float F12[9];                    /* as orbfe_search_for_triangulation */
+    float ep[2];
+} orbfe_tri_job;
+
+/* SearchForTriangulation(pKF1, jobs[c].kf2, vMatchedIndices, bOnlyStereo, bCoarse) for c in [0, n_jobs)
+ * in one call and one kernel launch, one workgroup per neighbour: the per-neighbour calls of
+ * LocalMapping::CreateNewMapPoints (LocalMapping.cc:388-470). kf1 and every kf2: resident keyframes of
+ * orbfe_keyframe_create_geom; mp1: [orbfe_keyframe_n(kf1)] GetMapPoint(idx) presence, host memory, read
+ * once per call. matches12: [n_jobs][orbfe_keyframe_n(kf1)]; nmatches: [n_jobs]. Row c and nmatches[c]
+ * are bit-identical to matches12 and the return value of orbfe_search_for_triangulation on the arrays
+ * the two handles were created from, with the same mp1, jobs[c].mp2, F12, ep, kf2's level_sigma2 and
+ * flags (so each row is searched against the mp1 given, whatever the other rows matched). A neighbour
+ * that does not fit one workgroup's LDS takes k_tri + k_bow_commit inside the same call on the resident
+ * arrays of both handles, without re-uploading either keyframe. A neighbour that shares no node with
+ * kf1, has no features or an empty FeatureVector gets the empty row. Complete on return, after one
+ * host wait.
+ * n_jobs == 0 returns ORBFE_OK. ORBFE_E_ARG, before any device work and before any write: n_jobs < 0, a
+ * NULL matches12 / nmatches / kf1 / jobs, a handle without geometry, a handle of another device, a NULL
+ * mp1 or mp2 of a keyframe with features, a two-camera kf1 or kf2 without bCoarse (as the single call),
+ * a handle whose FeatureVector names an index in two nodes (the single call refuses those arrays too).
+ * ORBFE_E_CAPACITY: more than 2^28 output words. Returns ORBFE_OK or a negative code. */
+int orbfe_search_for_triangulation_batch(const orbfe_keyframe* kf1, const int32_t* mp1, const orbfe_tri_job* jobs,
+                                         int32_t n_jobs, int32_t bOnlyStereo, int32_t bCoarse, int32_t checkOri,
+                                         int32_t* matches12, int32_t* nmatches);
 
 /* The caller's epipolar test of one keypoint pair of SearchForTriangulation (bCoarse false):
  * pCamera1->epipolarConstrain(pCamera2, kp1, kp2, R12, t12, pKF1->mvLevelSigma2[kp1.octave],
@@ -1161,6 +1207,11 @@ int orbfe_matcher_last_bow_batch(int32_t* out);
  * either side, no node shared with KF1, or a call that returned before any launch), out[2] took
  * k_bow_kfkf + k_bow_kfkf_commit_ang. */
 int orbfe_matcher_last_bow_kf_batch(int32_t* out);
+/* The same three counts for this thread's last orbfe_search_for_triangulation_batch: out[0] neighbours
+ * matched in k_tri_batch's one workgroup, out[1] got the empty row (NULL, no features or FeatureVector
+ * on either side, no node shared with KF1, or a call that returned before any launch), out[2] took
+ * k_tri + k_bow_commit on the resident arrays. All zero after a refused or empty call. */
+int orbfe_matcher_last_tri_batch(int32_t* out);
 /* Of this thread's last orbfe_search_by_projection_lastframe_slabs: out[0] frames searched in
  * k_sbp_track_batch's one workgroup, out[1] skipped (n_pts == 0 or no keypoints), out[2] over the
  * workgroup's capacity (nmatches[f] = ORBFE_E_CAPACITY). All zero after a refused or empty call. */

@@ -262,19 +262,41 @@ struct TriArgs {
     int bOnlyStereo, bCoarse;
     int two1, two2;        // KF1 / KF2 have a second camera (mpCamera2): bStereo false, no epipole test for KF1
 };
-__global__ __launch_bounds__(MT_NT) void k_tri(const int2* items, int nitems, const uint32_t* idx1s, const int* off2,
-                                               const uint32_t* idx2s, const OrbKeyPoint* k1, const OrbKeyPoint* k2,
-                                               const uint32_t* d1, const uint32_t* d2, const float* ur1,
-                                               const float* ur2, const int32_t* mp1, const int32_t* mp2,
-                                               const float* scale2, const float* sigma2_2, TriArgs a, int* out_idx) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= nitems) return;
-    const int2 it = items[t];
-    const unsigned i1 = idx1s[it.x];
-    if (mp1[i1] >= 0) return;
-    const bool bStereo1 = !a.two1 && ur1 && ur1[i1] >= 0;   // (!pKF1->mpCamera2 && mvuRight >= 0)
-    if (a.bOnlyStereo && !bStereo1) return;
-    const OrbKeyPoint kp1 = k1[i1];
+// Where the walk reads a keyframe's keypoints: the cv::KeyPoint array and mvuRight of a call's upload, or
+// the geometry block of a resident keyframe (orbfe_keyframe_create_geom: uright is -1 where the call's
+// "ur && !two" is false)
+struct TriKp {
+    float x, y;
+    int octave;
+};
+struct TriKeysUp {
+    const OrbKeyPoint* k;
+    const float* ur;   // NULL: monocular or a second camera
+    __device__ __forceinline__ bool stereo(unsigned i) const { return ur && ur[i] >= 0; }
+    __device__ __forceinline__ TriKp kp(unsigned i) const {
+        const OrbKeyPoint p = k[i];
+        return TriKp{p.x, p.y, p.octave};
+    }
+};
+struct TriKeysGeom {
+    const float4* g;
+    __device__ __forceinline__ bool stereo(unsigned i) const { return g[i].w >= 0; }
+    __device__ __forceinline__ TriKp kp(unsigned i) const {
+        const float4 p = g[i];
+        return TriKp{p.x, p.y, __float_as_int(p.z)};
+    }
+};
+// SearchForTriangulation's walk of one KF1 keypoint i1 through KF2 node entries [lo, hi) of idx2s
+// (ORBmatcher.cc:961-1095): the matched KF2 index or -1. dist > bestDist -> continue, so an equal distance
+// replaces: the last passing candidate of the smallest passing distance wins.
+template <class K1, class K2>
+__device__ __forceinline__ int tri_walk(unsigned i1, int lo, int hi, const uint32_t* idx2s, K1 k1, K2 k2,
+                                        const uint32_t* d1, const uint32_t* d2, const int32_t* mp1, const int32_t* mp2,
+                                        const float* scale2, const float* sigma2_2, const TriArgs& a) {
+    if (mp1[i1] >= 0) return -1;
+    const bool bStereo1 = !a.two1 && k1.stereo(i1);   // (!pKF1->mpCamera2 && mvuRight >= 0)
+    if (a.bOnlyStereo && !bStereo1) return -1;
+    const TriKp kp1 = k1.kp(i1);
     uint32_t q[8];
 #pragma unroll
     for (int w = 0; w < 8; w++) q[w] = d1[8 * i1 + w];
@@ -283,16 +305,16 @@ __global__ __launch_bounds__(MT_NT) void k_tri(const int2* items, int nitems, co
     const float lb = kp1.x * a.F[1] + kp1.y * a.F[4] + a.F[7];
     const float lc = kp1.x * a.F[2] + kp1.y * a.F[5] + a.F[8];
     int bestDist = MT_TH_LOW, bestIdx2 = -1;
-    for (int ib = off2[it.y]; ib < off2[it.y + 1]; ib++) {
+    for (int ib = lo; ib < hi; ib++) {
         const unsigned i2 = idx2s[ib];
         if (mp2[i2] >= 0) continue;
-        const bool bStereo2 = !a.two2 && ur2 && ur2[i2] >= 0;
+        const bool bStereo2 = !a.two2 && k2.stereo(i2);
         if (a.bOnlyStereo && !bStereo2) continue;
         int dist = 0;
 #pragma unroll
         for (int w = 0; w < 8; w++) dist += __popc(q[w] ^ d2[8 * i2 + w]);
         if (dist > MT_TH_LOW || dist > bestDist) continue;
-        const OrbKeyPoint kp2 = k2[i2];
+        const TriKp kp2 = k2.kp(i2);
         if (!bStereo1 && !bStereo2 && !a.two1) {
             const float distex = a.ep[0] - kp2.x, distey = a.ep[1] - kp2.y;
             if (distex * distex + distey * distey < 100 * scale2[kp2.octave]) continue;
@@ -308,6 +330,21 @@ __global__ __launch_bounds__(MT_NT) void k_tri(const int2* items, int nitems, co
         }
         if (ok) { bestIdx2 = (int)i2; bestDist = dist; }
     }
+    return bestIdx2;
+}
+// One thread per KF1 entry of a shared node (items: KF1 CSR position, KF2 node). Keys: TriKeysUp for a
+// call's uploaded keyframes, TriKeysGeom for resident ones (orbfe_search_for_triangulation_batch).
+template <class K1, class K2>
+__global__ __launch_bounds__(MT_NT) void k_tri(const int2* items, int nitems, const uint32_t* idx1s, const int* off2,
+                                               const uint32_t* idx2s, K1 k1, K2 k2, const uint32_t* d1,
+                                               const uint32_t* d2, const int32_t* mp1, const int32_t* mp2,
+                                               const float* scale2, const float* sigma2_2, TriArgs a, int* out_idx) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nitems) return;
+    const int2 it = items[t];
+    const unsigned i1 = idx1s[it.x];
+    const int bestIdx2 =
+        tri_walk(i1, off2[it.y], off2[it.y + 1], idx2s, k1, k2, d1, d2, mp1, mp2, scale2, sigma2_2, a);
     if (bestIdx2 >= 0) out_idx[i1] = bestIdx2;
 }
 
@@ -550,11 +587,12 @@ int orbfe_search_for_triangulation(const orbfe_frame* KF1, const int32_t* mp1, c
     ta.two1 = KF1->two_cams != 0;
     ta.two2 = KF2->two_cams != 0;
     fill(ms_ptr<int>(o_oi), n1, -1);
-    hipLaunchKernelGGL(k_tri, dim3((nitems + MT_NT - 1) / MT_NT), dim3(MT_NT), 0, s, ms_ptr<const int2>(o_items), nitems,
-                       ms_ptr<const uint32_t>(o_idx1), ms_ptr<const int>(o_off2), ms_ptr<const uint32_t>(o_idx2),
-                       ms_ptr<const OrbKeyPoint>(o_k1), ms_ptr<const OrbKeyPoint>(o_k2), ms_ptr<const uint32_t>(o_d1),
-                       ms_ptr<const uint32_t>(o_d2), u1 ? ms_ptr<const float>(o_u1) : nullptr,
-                       u2 ? ms_ptr<const float>(o_u2) : nullptr, ms_ptr<const int32_t>(o_mp1),
+    hipLaunchKernelGGL((k_tri<TriKeysUp, TriKeysUp>), dim3((nitems + MT_NT - 1) / MT_NT), dim3(MT_NT), 0, s,
+                       ms_ptr<const int2>(o_items), nitems, ms_ptr<const uint32_t>(o_idx1), ms_ptr<const int>(o_off2),
+                       ms_ptr<const uint32_t>(o_idx2),
+                       TriKeysUp{ms_ptr<const OrbKeyPoint>(o_k1), u1 ? ms_ptr<const float>(o_u1) : nullptr},
+                       TriKeysUp{ms_ptr<const OrbKeyPoint>(o_k2), u2 ? ms_ptr<const float>(o_u2) : nullptr},
+                       ms_ptr<const uint32_t>(o_d1), ms_ptr<const uint32_t>(o_d2), ms_ptr<const int32_t>(o_mp1),
                        ms_ptr<const int32_t>(o_mp2), ms_ptr<const float>(o_sc2), ms_ptr<const float>(o_sg2), ta,
                        ms_ptr<int>(o_oi));
     // the row holds the matched KF2 index itself (no handles)

@@ -1553,3 +1553,6 @@ int orbfe_descriptor_distance(const uint8_t* a, const uint8_t* b) {
 
 // Batched SearchByBoW(KF, F) over the same frames and the FeatureVector rows of the batched ComputeBoW.
 #include "orbfe_bow_slabs.hip"
+
+// Batched SearchForTriangulation(KF1, KF2) over resident keyframes with geometry (LocalMapping::CreateNewMapPoints).
+#include "orbfe_tri_batch.hip"

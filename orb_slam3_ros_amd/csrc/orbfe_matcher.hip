@@ -3242,9 +3242,13 @@ __device__ __forceinline__ void bow_walk_node(int a0, int a1, int b0, int b1, co
 // matched to own index i < n (-1: none), own(u, i) the angle of own index i = tid + u * MT_BOW_NT,
 // matched(j) that of matched index j, mp the matched side's handles; OWN_FIRST as in k_bow_commit.
 // The caller's s_hist is zeroed, s_n is 0 and a barrier has passed since the last write to match;
-// on return s_n is being counted: a barrier before it is read.
-template <bool OWN_FIRST, class OwnAng, class MatchedAng>
-__device__ __forceinline__ void bow_commit_rows(int n, const int* match, OwnAng own, MatchedAng matched, const int* mp,
+// on return s_n is being counted: a barrier before it is read. mp[j] is what the row holds for matched
+// index j: the handles, or RowIndex for j itself (SearchForTriangulation).
+struct RowIndex {
+    __device__ __forceinline__ int operator[](int j) const { return j; }
+};
+template <bool OWN_FIRST, class OwnAng, class MatchedAng, class Handles>
+__device__ __forceinline__ void bow_commit_rows(int n, const int* match, OwnAng own, MatchedAng matched, Handles mp,
                                                 int checkOri, int* out, int* s_hist, unsigned* s_keep, int* s_n) {
     const int tid = threadIdx.x;
     int sidx[MT_BOW_FR], bin[MT_BOW_FR];
@@ -3469,6 +3473,15 @@ __global__ __launch_bounds__(MT_BOW_NT) void k_bow_batch(BowBatchIn in) {
     if (tid == 0) in.nm[c] = s_n;   // the host reads the rows after a stream synchronisation
 }
 // the angles of a device-resident keyframe's keypoints, gathered into its pack at create
+// the keypoint records of a resident keyframe's geometry block from a device view's keys (the octave is
+// clamped to the level tables: a device view cannot be checked on the host)
+__global__ void k_kf_geom_pack(const OrbKeyPoint* keys, const float* uright, int n, int nlevels, float4* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const OrbKeyPoint k = keys[i];
+    const int oct = k.octave < 0 ? 0 : (k.octave >= nlevels ? nlevels - 1 : k.octave);
+    out[i] = make_float4(k.x, k.y, __int_as_float(oct), uright ? uright[i] : -1.0f);
+}
 __global__ void k_kf_angles(const OrbKeyPoint* keys, int n, float* ang) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) ang[i] = keys[i].angle;
@@ -4746,7 +4759,19 @@ struct orbfe_keyframe {
     int nvec = 0;
     int o_off = 0, o_idx = 0, o_ang = 0, o_desc = 0;
     std::vector<uint32_t> node_ids;
+    // orbfe_keyframe_create_geom only: a second allocation, [x, y, octave, uright per keypoint (16 bytes
+    // each) | scale_factors | level_sigma2], the two level tables at 16-byte offsets (kf_geom_vec)
+    bool has_geom = false;
+    bool two = false;          // two_cams: every uright is -1
+    int nlevels = 0;
+    uint8_t* geom = nullptr;   // has_geom && n > 0
+    int gvec = 0;              // its 16-byte words
+    int nki = 0;               // entries of the FeatureVector
+    std::vector<int32_t> offs; // has_geom: the CSR offsets on the host too (k_tri's item list is joined there)
 };
+// 16-byte words of a geometry block, and of one of its level tables
+__host__ __device__ inline int kf_geom_lvec(int nlevels) { return (nlevels + 3) / 4; }
+__host__ __device__ inline int kf_geom_vec(int n, int nlevels) { return n + 2 * kf_geom_lvec(nlevels); }
 
 extern "C" {
 
@@ -5102,11 +5127,22 @@ int orbfe_search_by_bow(const orbfe_keypoint* kf_keys, const uint8_t* kf_desc, c
     return nm;
 }
 
-int orbfe_keyframe_create(const orbfe_frame* KF, const orbfe_feature_vector* fv, orbfe_keyframe** out) {
+}  // extern "C"
+
+namespace {
+// orbfe_keyframe_create (level_sigma2 == NULL: the pack alone) and orbfe_keyframe_create_geom
+int kf_create(const orbfe_frame* KF, const orbfe_feature_vector* fv, const float* level_sigma2, bool geom,
+              orbfe_keyframe** out) {
     if (!out) return ORBFE_E_ARG;
     *out = nullptr;
     if (!KF || !fv || KF->n < 0 || fv->n_nodes < 0 || (KF->n > 0 && (!KF->keys || !KF->desc))) return ORBFE_E_ARG;
     const int n = KF->n, nn = fv->n_nodes;
+    if (geom) {   // the fields the geometry block is built from; refused before any allocation
+        if (KF->nlevels < 1 || !KF->scale_factors || !level_sigma2) return ORBFE_E_ARG;
+        if (!KF->device)
+            for (int i = 0; i < n; i++)
+                if (KF->keys[i].octave < 0 || KF->keys[i].octave >= KF->nlevels) return ORBFE_E_ARG;
+    }
     bool repeats = false;   // an index in several nodes is accepted here and refused by the KF-KF search
     if (nn > 0 && (!fv_shape_ok(fv) || !fv_indices_unique(fv, n, &repeats))) return ORBFE_E_ARG;
     const int nki = nn > 0 ? fv->offsets[nn] : 0;
@@ -5120,6 +5156,11 @@ int orbfe_keyframe_create(const orbfe_frame* KF, const orbfe_feature_vector* fv,
     kf->n = n;
     kf->nn = nn;
     if (nn > 0) kf->node_ids.assign(fv->node_ids, fv->node_ids + nn);
+    kf->has_geom = geom;
+    kf->two = geom && KF->two_cams != 0;
+    kf->nlevels = geom ? KF->nlevels : 0;
+    kf->nki = nki;
+    if (geom && nn > 0) kf->offs.assign(fv->offsets, fv->offsets + nn + 1);
     if (n == 0) {   // nothing to match: no pack, every search gives the empty row
         *out = kf.release();
         return ORBFE_OK;
@@ -5147,26 +5188,74 @@ int orbfe_keyframe_create(const orbfe_frame* KF, const orbfe_feature_vector* fv,
     struct Guard {
         uint8_t* p;
         ~Guard() { if (p) (void)hipFree(p); }
-    } guard{pack};
+    } guard{pack}, gguard{nullptr};
     HIPCHK(hipMemcpy(pack, h.data(), o_desc, hipMemcpyHostToDevice));
+    // the geometry block: keypoint records, then mvScaleFactors and mvLevelSigma2
+    uint8_t* gblk = nullptr;
+    const int nlv = geom ? KF->nlevels : 0, lvec = kf_geom_lvec(nlv), gvec = kf_geom_vec(n, nlv);
+    const bool ur = geom && KF->uright && !KF->two_cams;
+    if (geom) {
+        HIPCHK(hipMalloc((void**)&gblk, (size_t)gvec * 16));
+        gguard.p = gblk;
+        std::vector<float> tab((size_t)lvec * 8, 0.f);
+        memcpy(tab.data() + (size_t)lvec * 4, level_sigma2, (size_t)nlv * 4);
+        if (!KF->device) memcpy(tab.data(), KF->scale_factors, (size_t)nlv * 4);
+        HIPCHK(hipMemcpy(gblk + (size_t)n * 16, tab.data(), (size_t)lvec * 32, hipMemcpyHostToDevice));
+    }
     if (KF->device) {   // a view of orbfe_frame_device_view: device to device, no host round trip
         hipLaunchKernelGGL(k_kf_angles, dim3((n + 255) / 256), dim3(256), 0, nullptr, (const OrbKeyPoint*)KF->keys, n,
                            (float*)(pack + o_ang));
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(pack + o_desc, KF->desc, (size_t)n * 32, hipMemcpyDeviceToDevice, nullptr));
+        if (geom) {
+            hipLaunchKernelGGL(k_kf_geom_pack, dim3((n + 255) / 256), dim3(256), 0, nullptr,
+                               (const OrbKeyPoint*)KF->keys, ur ? KF->uright : nullptr, n, nlv, (float4*)gblk);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(gblk + (size_t)n * 16, KF->scale_factors, (size_t)nlv * 4, hipMemcpyDeviceToDevice,
+                                  nullptr));
+        }
         HIPCHK(hipStreamSynchronize(nullptr));
     } else {
         HIPCHK(hipMemcpy(pack + o_desc, KF->desc, (size_t)n * 32, hipMemcpyHostToDevice));
+        if (geom) {
+            std::vector<float4> rec(n);
+            for (int i = 0; i < n; i++) {
+                const orbfe_keypoint& k = KF->keys[i];
+                int32_t oct = k.octave;
+                float o;
+                memcpy(&o, &oct, 4);
+                rec[i] = make_float4(k.x, k.y, o, ur ? KF->uright[i] : -1.0f);
+            }
+            HIPCHK(hipMemcpy(gblk, rec.data(), (size_t)n * 16, hipMemcpyHostToDevice));
+        }
     }
     guard.p = nullptr;
+    gguard.p = nullptr;
     kf->pack = pack;
+    kf->geom = gblk;
+    kf->gvec = geom ? gvec : 0;
     *out = kf.release();
     return ORBFE_OK;
 }
+}  // namespace
+
+extern "C" {
+
+int orbfe_keyframe_create(const orbfe_frame* KF, const orbfe_feature_vector* fv, orbfe_keyframe** out) {
+    return kf_create(KF, fv, nullptr, false, out);
+}
+
+int orbfe_keyframe_create_geom(const orbfe_frame* KF, const orbfe_feature_vector* fv, const float* level_sigma2,
+                               orbfe_keyframe** out) {
+    return kf_create(KF, fv, level_sigma2, true, out);
+}
+
+int orbfe_keyframe_has_geom(const orbfe_keyframe* kf) { return kf ? (kf->has_geom ? 1 : 0) : ORBFE_E_ARG; }
 
 void orbfe_keyframe_destroy(orbfe_keyframe* kf) {
     if (!kf) return;
     if (kf->pack) (void)hipFree(kf->pack);
+    if (kf->geom) (void)hipFree(kf->geom);
     delete kf;
 }
 

@@ -332,19 +332,60 @@ class KeyFrameFeatures:
     device. The arrays may be released after construction; close() (or the finaliser) frees the HBM
     copy and must not run while a search uses the object."""
 
-    def __init__(self, frame, featvec: FeatureVector):
+    def __init__(self, frame, featvec: FeatureVector, level_sigma2=None):
+        """level_sigma2 (mvLevelSigma2, one float per level of frame.scale_factors): the keyframe also keeps
+        its geometry in HBM (keypoint positions, octaves, mvuRight, the level tables; orbfe_keyframe_create_geom)
+        and serves ORBmatcher.SearchForTriangulationBatch."""
         import weakref
         lib = _lib.load()
         h = ctypes.c_void_p()
-        _lib.check(lib.orbfe_keyframe_create(frame.ref(), featvec.ref(), ctypes.byref(h)), "KeyFrameFeatures")
+        if level_sigma2 is None:
+            _lib.check(lib.orbfe_keyframe_create(frame.ref(), featvec.ref(), ctypes.byref(h)), "KeyFrameFeatures")
+        else:
+            sg = np.ascontiguousarray(level_sigma2, np.float32).reshape(-1)
+            if len(sg) < int(frame.c.nlevels):
+                raise ValueError("level_sigma2 needs one entry per level")
+            _lib.check(lib.orbfe_keyframe_create_geom(frame.ref(), featvec.ref(), sg.ctypes.data, ctypes.byref(h)),
+                       "KeyFrameFeatures")
         self.handle = h.value
         self.N = int(lib.orbfe_keyframe_n(self.handle))
         self._fin = weakref.finalize(self, lib.orbfe_keyframe_destroy, self.handle)
+
+    @property
+    def has_geom(self) -> bool:
+        if self.handle is None:
+            raise ValueError("KeyFrameFeatures is closed")
+        return bool(_lib.check(_lib.load().orbfe_keyframe_has_geom(self.handle), "has_geom"))
 
     def close(self):
         if self.handle is not None:
             self._fin()
             self.handle = None
+
+
+class TriJob(ctypes.Structure):
+    """struct orbfe_tri_job: one neighbour of ORBmatcher.SearchForTriangulationBatch (64 bytes)."""
+    _fields_ = [("kf2", ctypes.c_void_p), ("mp2", ctypes.c_void_p), ("F12", ctypes.c_float * 9),
+                ("ep", ctypes.c_float * 2)]
+
+    @staticmethod
+    def make(kf2, mp2=None, F12=None, ep=None):
+        """kf2: KeyFrameFeatures with geometry, or None: the neighbour is skipped (its row is -1). mp2: int32
+        [kf2.N] GetMapPoint(idx) presence; F12 (3x3) and ep (2,) as SearchForTriangulation takes them. The
+        job keeps its arrays and the keyframe alive."""
+        j = TriJob()
+        j._kf = kf2
+        j._mp = None
+        if kf2 is None:
+            return j
+        if kf2.handle is None:
+            raise ValueError("KeyFrameFeatures is closed")
+        j.kf2 = kf2.handle
+        j._mp = _i32(np.ascontiguousarray(mp2, np.int32), kf2.N, "mp2")
+        j.mp2 = j._mp.ctypes.data if kf2.N else None
+        j.F12[:] = [float(v) for v in np.asarray(F12, np.float32).reshape(9)]
+        j.ep[:] = [float(v) for v in np.asarray(ep, np.float32).reshape(2)]
+        return j
 
 
 def _i32(a, n, what):
@@ -782,6 +823,37 @@ class ORBmatcher:
             sg.ctypes.data, int(bOnlyStereo), int(bCoarse), int(self.mbCheckOrientation), out.ctypes.data),
             "SearchForTriangulation")
         return n, out
+
+    # the SearchForTriangulation(mpCurrentKeyFrame, pKF2, ...) calls of LocalMapping::CreateNewMapPoints
+    # (LocalMapping.cc:388-470) in one call over resident keyframes with geometry
+    def SearchForTriangulationBatch(self, kf1, mp1, jobs, bOnlyStereo=False, bCoarse=False):
+        """kf1: KeyFrameFeatures(frame, featvec, level_sigma2) of the current keyframe; mp1: int32 [kf1.N]
+        GetMapPoint(idx) presence (handle or -1); jobs: TriJob per neighbour. Returns (nmatches int32 [J],
+        matches12 int32 [J, kf1.N]: KF2 index or -1); row c equals SearchForTriangulation on neighbour c
+        with the same mp1."""
+        if kf1 is None or kf1.handle is None:
+            raise ValueError("KeyFrameFeatures is closed")
+        J = len(jobs)
+        m1 = _i32(np.ascontiguousarray(mp1, np.int32), kf1.N, "mp1")
+        arr = (TriJob * max(J, 1))()
+        for c, j in enumerate(jobs):
+            if not isinstance(j, TriJob):
+                raise ValueError("jobs must be TriJob records")
+            ctypes.memmove(ctypes.byref(arr, c * ctypes.sizeof(TriJob)), ctypes.byref(j), ctypes.sizeof(TriJob))
+        out = np.full((J, kf1.N), -1, np.int32)
+        nm = np.zeros(J, np.int32)
+        if J:
+            _lib.check(self._lib.orbfe_search_for_triangulation_batch(
+                kf1.handle, m1.ctypes.data if kf1.N else None, arr, J, int(bool(bOnlyStereo)), int(bool(bCoarse)),
+                int(self.mbCheckOrientation), out.ctypes.data, nm.ctypes.data), "SearchForTriangulation(batch)")
+        return nm, out
+
+    @staticmethod
+    def last_tri_batch():
+        """(one workgroup, empty row, HBM fallback) job counts of this thread's last SearchForTriangulationBatch."""
+        w = np.zeros(3, np.int32)
+        _lib.check(_lib.load().orbfe_matcher_last_tri_batch(w.ctypes.data), "last_tri_batch")
+        return tuple(int(v) for v in w)
 
     # SearchForTriangulation with bCoarse = false and the caller's epipolar test (keyframes with a
     # second camera: KannalaBrandt8::epipolarConstrain on the host, ORBmatcher.cc:1036-1074)

@@ -370,6 +370,88 @@ def synth_sim3_pair(rng, n1: int, extra2: float = 0.2, scale: float = 1.0, nleve
     return KF1, KF2, pts1, pts2, cam1, cam2, S12, S21, src
 
 
+def synth_tri_neighbour(rng, KF1: MatchFrame, pts1, cam1: KFCamera, extra2: float = 0.2, nlevels: int = 8,
+                        sf: float = 1.2):
+    """Another covisible neighbour of synth_sim3_pair's KF1 (the keyframes of one CreateNewMapPoints call):
+    a keyframe at a new pose near cam1 observing KF1's points pts1, by synth_sim3_pair's recipe. Returns
+    (KF2, cam2, src) with src[j] = the KF1 keypoint KF2 keypoint j observes (-1 if new)."""
+    fx, fy, cx, cy, w, h = cam1.fx, cam1.fy, cam1.cx, cam1.cy, int(KF1.bounds[1]), int(KF1.bounds[3])
+    n1 = KF1.N
+    R1, t1 = cam1.Tcw.rotation(), np.array(cam1.Tcw.t[:], np.float64)
+    R2 = _rand_rotation(rng, 8.0) @ R1
+    t2 = t1 + rng.normal(scale=0.3, size=3)
+    cam2 = KFCamera.make(Pose.se3(R2, t2), fx, fy, cx, cy)
+    Pw = pts1["pos"].astype(np.float64)
+    Pc2 = Pw @ R2.T + t2
+    d2 = np.linalg.norm(Pc2, axis=1)
+    pred2 = np.clip(np.ceil(np.log(pts1["max_dist"].astype(np.float64) / d2) / np.log(sf)), 0, nlevels - 1).astype(np.int32)
+    u2 = fx * Pc2[:, 0] / Pc2[:, 2] + cx + rng.normal(0, 0.7, n1)
+    v2 = fy * Pc2[:, 1] / Pc2[:, 2] + cy + rng.normal(0, 0.7, n1)
+    vis = (Pc2[:, 2] > 0) & (u2 >= 0) & (u2 < w) & (v2 >= 0) & (v2 < h) & (rng.random(n1) < 0.85)
+    idx = np.nonzero(vis)[0]
+    n_new = int(len(idx) * extra2)
+    n2 = len(idx) + n_new
+    k2 = np.zeros(n2, KEYPOINT_DTYPE)
+    k2["x"][:len(idx)] = u2[idx]
+    k2["y"][:len(idx)] = v2[idx]
+    k2["octave"][:len(idx)] = np.maximum(pred2[idx] - (rng.random(len(idx)) < 0.3), 0)
+    k2["x"][len(idx):] = rng.uniform(0, w - 1, n_new)
+    k2["y"][len(idx):] = rng.uniform(0, h - 1, n_new)
+    k2["octave"][len(idx):] = rng.choice(nlevels, n_new, p=level_weights(nlevels))
+    sfs = scale_factors(nlevels)
+    k2["size"] = (31.0 * sfs[k2["octave"]]).astype(np.float32)
+    k2["angle"] = np.mod(np.concatenate([KF1.keys["angle"][idx], rng.uniform(0, 360, n_new)]) + 15.0, 360.0)
+    k2["response"] = 20.0
+    k2["class_id"] = -1
+    desc = np.concatenate([flip_bits(rng, KF1.desc[idx], 0.06), rng.integers(0, 256, (n_new, 32), dtype=np.uint8)])
+    perm = rng.permutation(n2)
+    src = np.concatenate([idx, np.full(n_new, -1)])[perm]
+    return MatchFrame(k2[perm], desc[perm], KF1.bounds, sfs, None, KF1.mbf), cam2, src
+
+
+class TriNeighbour:
+    """One neighbour of synth_tri_scene: the keyframe, its FeatureVector, GetMapPoint presence, F12, the
+    epipole and mvLevelSigma2, as SearchForTriangulation(KF1, KF2) takes them."""
+
+    def __init__(self, K, fv, mp, F12, ep, sigma2):
+        self.K, self.fv, self.mp, self.F12, self.ep, self.sigma2 = K, fv, mp, F12, ep, sigma2
+
+
+def synth_tri_scene(rng, n1: int, n_neighbours: int, words: int, stereo: bool = False, occupied: float = 0.4):
+    """LocalMapping::CreateNewMapPoints' inputs: a current keyframe of n1 features and n_neighbours covisible
+    keyframes at their own poses (synth_tri_neighbour), each observed feature in its source's vocabulary
+    node; `occupied` of the slots on either side already hold a map point; stereo: 60 % of the keypoints
+    on both sides have mvuRight >= 0. Returns (KF1, fv1, mp1, sigma2_1, [TriNeighbour])."""
+    K1, _, pts1, _, cam1, *_ = synth_sim3_pair(rng, n1)
+
+    def side(K):
+        if not stereo:
+            return K
+        ur = np.where(rng.random(K.N) < 0.6, K.keys["x"] - 10, -1).astype(np.float32)
+        return MatchFrame(K.keys, K.desc, K.bounds, K.scale_factors, ur, K.mbf)
+
+    def fv(wd):
+        d = {}
+        for i, x in enumerate(wd.tolist()):
+            d.setdefault(int(x) * 7 + 3, []).append(i)   # sparse node ids
+        return FeatureVector(d)
+
+    def presence(n):
+        return np.where(rng.random(n) < occupied, 5, -1).astype(np.int32)
+
+    K1 = side(K1)
+    w1 = rng.integers(0, words, K1.N)
+    out = []
+    for _ in range(n_neighbours):
+        K2, cam2, src = synth_tri_neighbour(rng, K1, pts1, cam1)
+        K2 = side(K2)
+        w2 = rng.integers(0, words, K2.N)
+        w2[src >= 0] = w1[src[src >= 0]]
+        F12, ep = fundamental_12(cam1, cam2)
+        out.append(TriNeighbour(K2, fv(w2), presence(K2.N), F12, ep, (K2.scale_factors * K2.scale_factors).astype(np.float32)))
+    return K1, fv(w1), presence(K1.N), (K1.scale_factors * K1.scale_factors).astype(np.float32), out
+
+
 def fundamental_12(cam1: KFCamera, cam2: KFCamera):
     """F12 = K1^-T [t12]x R12 K2^-1 and the epipole ep = project2(T2w * Cw1) (ORBmatcher.cc:914-920,
     Pinhole.cpp:107-112), computed in float64 and rounded to float."""

@@ -65,12 +65,19 @@ struct KeyFrameCache {
         kf.n = pKF->N;
         kf.keys = reinterpret_cast<const orbfe_keypoint*>(pKF->mpCamera2 ? keys.data() : pKF->mvKeysUn.data());
         kf.desc = pKF->mDescriptors.data;
+        // the geometry SearchForTriangulation reads besides (shim/LocalMapping_orbfe.cc): mvuRight, the
+        // octaves and the level tables are as immutable as the descriptors
+        kf.uright = pKF->mvuRight.empty() ? nullptr : pKF->mvuRight.data();
+        kf.nlevels = pKF->mnScaleLevels;
+        kf.scale_factors = pKF->mvScaleFactors.data();
+        kf.two_cams = pKF->mpCamera2 ? 1 : 0;
         vector<uint32_t> ids, idx;
         vector<int32_t> off;
         flatten(pKF->mFeatVec, ids, off, idx);
         const orbfe_feature_vector fv{(int32_t)ids.size(), ids.data(), off.data(), idx.data()};
         orbfe_keyframe* h = nullptr;
-        if (orbfe_keyframe_create(&kf, &fv, &h) != ORBFE_OK) return nullptr;
+        if ((int)pKF->mvLevelSigma2.size() < kf.nlevels) return nullptr;
+        if (orbfe_keyframe_create_geom(&kf, &fv, pKF->mvLevelSigma2.data(), &h) != ORBFE_OK) return nullptr;
         lock_guard<mutex> lk(mu);
         auto ins = map.emplace(pKF, h);
         if (!ins.second) {   // another thread created it meanwhile
@@ -111,6 +118,8 @@ void per_candidate(const vector<KeyFrame*>& vpKFs, Frame& F, float nnratio, bool
 }  // namespace
 
 void ForgetKeyFrameFeatures(KeyFrame* pKF) { cache().forget(pKF); }
+
+const orbfe_keyframe* ResidentKeyFrame(KeyFrame* pKF) { return cache().get(pKF); }
 
 void SearchByBoWCandidates(const vector<KeyFrame*>& vpCandidateKFs, Frame& F, float nnratio, bool checkOri,
                            vector<vector<MapPoint*>>& vvpMapPointMatches, vector<int>& vnMatches) {

@@ -6,6 +6,8 @@
 
 #include "Frame.h"   // Sophus::SE3f
 
+struct orbfe_keyframe;   // <orbfe.h>
+
 namespace ORB_SLAM3 {
 
 class KeyFrame;
@@ -30,5 +32,9 @@ void SearchByProjectionCandidates(Frame& F, const std::vector<KeyFrame*>& vpKFs,
 // Drops pKF's device-resident features (call it where the KeyFrame is deleted or its mFeatVec /
 // mDescriptors are rebuilt); must not run while SearchByBoWCandidates uses pKF.
 void ForgetKeyFrameFeatures(KeyFrame* pKF);
+
+// pKF's resident features with geometry (orbfe_keyframe_create_geom), created on first use and shared by
+// every search of this file and of shim/LocalMapping_orbfe.cc; NULL when the library refuses the keyframe.
+const ::orbfe_keyframe* ResidentKeyFrame(KeyFrame* pKF);
 
 }  // namespace ORB_SLAM3
