@@ -421,6 +421,21 @@ int orbfe_keyframe_create_geom(const orbfe_frame* KF, const orbfe_feature_vector
                                orbfe_keyframe** out);
 int orbfe_keyframe_has_geom(const orbfe_keyframe* kf);
 
+/* A resident keyframe with its search grid: everything orbfe_keyframe_create_geom keeps, in the same
+ * pack and geometry block (so the handle is valid wherever a handle with geometry is accepted), and in
+ * a third device block what Fuse reads besides: mnMinX / mnMaxX / mnMinY / mnMaxY and mbf (KF->min_x ..
+ * max_y, mbf), two_cams / NLeft, mvInvLevelSigma2 (formed here in float as 1.0f / level_sigma2[l], as
+ * KeyFrame forms it) and the level-restricted cell grids the single calls rebuild per call (grid l: the
+ * keypoints of octave l - 1 or l, in (cell, index) order; a two-camera keyframe's mvKeysRight in a second
+ * set of cells). The grids depend only on data fixed at the keyframe's construction and are built once,
+ * here. Reads what orbfe_keyframe_create_geom reads, and min_x, max_x, min_y, max_y, mbf, nleft.
+ * ORBFE_E_ARG, before any allocation: what orbfe_keyframe_create_geom refuses, max_x <= min_x or max_y <=
+ * min_y, n > 8192 (the limit of the single calls' frames), a two-camera KF with nleft outside [0, n].
+ * orbfe_keyframe_has_grid: 1 for such a handle, 0 for any other, ORBFE_E_ARG for NULL. */
+int orbfe_keyframe_create_grid(const orbfe_frame* KF, const orbfe_feature_vector* fv, const float* level_sigma2,
+                               orbfe_keyframe** out);
+int orbfe_keyframe_has_grid(const orbfe_keyframe* kf);
+
 /* SearchByBoW(kfs[c], F, out[c]) for c in [0, n_kfs) in one call and one kernel launch, one workgroup
  * per candidate. kfs[c] == NULL is a discarded candidate (pKF->isBad()): its row is all -1 and
  * nmatches[c] = 0. kf_mp[c]: [orbfe_keyframe_n(kfs[c])] map-point handles with bad / NULL points as
@@ -887,6 +902,39 @@ int orbfe_fuse_rig(const orbfe_frame* KF, const orbfe_kf_camera* cam, const orbf
                    const float* inv_level_sigma2, const orbfe_map_point_3d* pts, int32_t n, float th, int32_t sim3,
                    int32_t bRight, int32_t* best_idx, int32_t* best_dist);
 
+/* One (keyframe, pose) target of orbfe_fuse_batch. 120 bytes. */
+typedef struct orbfe_fuse_job {
+    const orbfe_keyframe* kf;        /* resident, with its grid (orbfe_keyframe_create_grid); NULL: the
+                                        keyframe is skipped (isBad()): its row is all -1, nfused 0, and the
+                                        other fields are not read */
+    const uint8_t* skip;             /* [n] host bytes, nonzero = the point is not searched in THIS keyframe
+                                        (IsInKeyFrame(kf), resp. already in kf->GetMapPoints()); NULL = none */
+    orbfe_kf_camera cam;             /* GetPose() / Ow of this keyframe, or the SE3 made from its Scw; with
+                                        bRight GetRightPose() / GetRightCameraCenter() (as orbfe_fuse_rig) */
+    orbfe_camera_model model;        /* pCamera. ORBFE_CAM_PINHOLE with params {cam.fx, cam.fy, cam.cx,
+                                        cam.cy} is orbfe_fuse_rig's model == NULL */
+    int32_t bRight;                  /* search the right cells; needs sim3 == 0 and a two-camera kf */
+} orbfe_fuse_job;
+
+/* The search half of Fuse (orbfe_fuse_rig) for every target keyframe of LocalMapping::SearchInNeighbors
+ * (LocalMapping.cc:765-775: Fuse(pKFi, vpMapPointMatches), and again with bRight for a two-camera pKFi)
+ * or of LoopClosing::SearchAndFuse (LoopClosing.cc:3446-3530: Fuse(pKF, Scw, vpPoints, 4, vpReplacePoints),
+ * sim3 = 1) in one call and one kernel launch over resident keyframes: no keyframe is uploaded, no grid is
+ * rebuilt, pts (host memory) is uploaded once for all jobs, and the call waits on the host once.
+ * best_idx, best_dist: [n_jobs][n]; nfused: [n_jobs]. Row c and nfused[c] are bit-identical to best_idx,
+ * best_dist and the return value of orbfe_fuse_rig on the arrays handle c was created from, with
+ * jobs[c].cam and model, inv_level_sigma2[l] = 1.0f / level_sigma2[l], th, sim3, jobs[c].bRight, and pts in
+ * which the points at skip[i] != 0 carry ORBFE_MP_SKIP. Rows never affect each other: every row is
+ * searched against the gates given (INTEGRATION.md says why the caller may then commit job by job). A
+ * keyframe without features gets the empty row. n_jobs == 0 or n == 0 returns ORBFE_OK.
+ * ORBFE_E_ARG, before any device work and before any write: n_jobs < 0 or n < 0; a NULL jobs or nfused with
+ * n_jobs > 0; a NULL pts, best_idx or best_dist with n_jobs > 0 and n > 0; a handle without a grid or of
+ * another device; a pose whose kind is neither ORBFE_SE3 nor ORBFE_SIM3; a model type other than pinhole or
+ * KannalaBrandt8; bRight with sim3 or on a single-camera keyframe. ORBFE_E_CAPACITY: more than 2^28 output
+ * words. Returns ORBFE_OK or a negative code. */
+int orbfe_fuse_batch(const orbfe_fuse_job* jobs, int32_t n_jobs, const orbfe_map_point_3d* pts, int32_t n, float th,
+                     int32_t sim3, int32_t* best_idx, int32_t* best_dist, int32_t* nfused);
+
 /* SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (ORBmatcher.cc:427-523) and,
  * with point_kfs != NULL, the vpPointsKFs / vpMatchedKF overload (:525-646). cam->Tcw is the SE3
  * the reference builds from Scw; matched = vpMatched handles [KF->n] (in/out), matched_kf =
@@ -1212,6 +1260,10 @@ int orbfe_matcher_last_bow_kf_batch(int32_t* out);
  * on either side, no node shared with KF1, or a call that returned before any launch), out[2] took
  * k_tri + k_bow_commit on the resident arrays. All zero after a refused or empty call. */
 int orbfe_matcher_last_tri_batch(int32_t* out);
+/* Of this thread's last orbfe_fuse_batch: out[0] jobs searched by k_fuse_batch, out[1] jobs that got the
+ * empty row (a NULL handle, a keyframe without features, or a call without points), out[2] workgroups of
+ * the launch (0: the call ended before it). All zero after a refused or empty call. */
+int orbfe_matcher_last_fuse_batch(int32_t* out);
 /* Of this thread's last orbfe_search_by_projection_lastframe_slabs: out[0] frames searched in
  * k_sbp_track_batch's one workgroup, out[1] skipped (n_pts == 0 or no keypoints), out[2] over the
  * workgroup's capacity (nmatches[f] = ORBFE_E_CAPACITY). All zero after a refused or empty call. */

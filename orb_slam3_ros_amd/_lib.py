@@ -169,6 +169,10 @@ _SIGS = {
     "orbfe_keyframe_has_geom": (_c_int, [_vp]),
     "orbfe_search_for_triangulation_batch": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
     "orbfe_matcher_last_tri_batch": (_c_int, [_vp]),
+    "orbfe_keyframe_create_grid": (_c_int, [_vp, _vp, _vp, ctypes.POINTER(_vp)]),
+    "orbfe_keyframe_has_grid": (_c_int, [_vp]),
+    "orbfe_fuse_batch": (_c_int, [_vp, _c_int, _vp, _c_int, _c_float, _c_int, _vp, _vp, _vp]),
+    "orbfe_matcher_last_fuse_batch": (_c_int, [_vp]),
     "orbfe_kfdb_detect_nbest": (_c_int, [_vp, _vp, _vp, _c_int, _vp, _c_int, _c_int, _vp, _c_int, _c_int, KF_INFO_FN,
                                          _vp, _vp, _vp, _vp, _vp]),
     "orbfe_search_by_projection_lastframe_slabs": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp,

@@ -12,7 +12,7 @@ SOURCES = ["orbfe_engine.hip"]
 DEPS = ["orbfe_engine.hip", "orbfe_kernels.hip", "orbfe_types.h", "glibc_sincosf.h", "stl_sort.h",
         "brief_pattern.h", "orbfe_matcher.hip", "orbfe_bow.hip", "glibc_logf.h", "glibc_atan2f.h", "orbfe_remap.hip", "orbfe_backend.hip",
         "orbfe_rgbd.hip", "orbfe_kfdb.hip", "orbfe_bow_batch.hip", "orbfe_place.hip", "orbfe_track_batch.hip",
-        "orbfe_local_batch.hip", "orbfe_bow_slabs.hip", "orbfe_tri_batch.hip"]
+        "orbfe_local_batch.hip", "orbfe_bow_slabs.hip", "orbfe_tri_batch.hip", "orbfe_fuse_batch.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 

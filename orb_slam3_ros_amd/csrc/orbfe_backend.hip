@@ -124,14 +124,12 @@ struct KfProj {
     int level;             // -1: rejected before the search
 };
 
-__global__ __launch_bounds__(MT_NT) void k_kf_geom(KfGeom g, const orbfe_map_point_3d* pts, int n,
-                                                   const uint8_t* skip, KfProj* out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+// One point of the geometry pass: the projection record of pts[i] (level -1: rejected before the search).
+// k_kf_geom and k_fuse_batch both run this body.
+__device__ __forceinline__ KfProj kf_project(const KfGeom& g, const orbfe_map_point_3d& mp, bool skipped) {
     KfProj r{0.f, 0.f, 0.f, -1};
-    const orbfe_map_point_3d& mp = pts[i];
     do {
-        if (mp.id < 0 || (mp.flags & g.skip_flags) || (skip && skip[i])) break;
+        if (mp.id < 0 || (mp.flags & g.skip_flags) || skipped) break;
         const float P[3] = {mp.pos[0], mp.pos[1], mp.pos[2]};
         float pc[3];
         be_pose_apply(g.T, P, pc);
@@ -179,7 +177,72 @@ __global__ __launch_bounds__(MT_NT) void k_kf_geom(KfGeom g, const orbfe_map_poi
         r.ur = u - g.mbf * invz;
         r.level = nScale;
     } while (0);
-    out[i] = r;
+    return r;
+}
+
+__global__ __launch_bounds__(MT_NT) void k_kf_geom(KfGeom g, const orbfe_map_point_3d* pts, int n,
+                                                   const uint8_t* skip, KfProj* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = kf_project(g, pts[i], skip && skip[i]);
+}
+
+// A resident keyframe as the area walk reads it (orbfe_keyframe_create_grid): the bounds and cell sizes
+// of FrameDev under the same names, the keypoints as the geometry block's records (x, y, octave, mvuRight
+// or -1 in one 16-byte load), the descriptors of the pack.
+struct KfGridKp {
+    float x, y;
+    int octave;
+    float ur;
+};
+struct KfGridKeys {
+    const float4* g;
+    __device__ __forceinline__ KfGridKp operator[](int i) const {
+        const float4 p = g[i];
+        return KfGridKp{p.x, p.y, __float_as_int(p.z), p.w};
+    }
+};
+struct KfGridFrame {
+    float minx, miny, invw, invh;
+    KfGridKeys keys;
+    const uint32_t* desc;
+};
+// mvuRight[idx] of the candidate, false where the reference takes the monocular gate (no mvuRight, or < 0)
+__device__ __forceinline__ bool kf_uright(const FrameDev& fr, int idx, const OrbKeyPoint&, float& ur) {
+    if (!fr.uright) return false;
+    ur = fr.uright[idx];
+    return ur >= 0;
+}
+__device__ __forceinline__ bool kf_uright(const KfGridFrame&, int, const KfGridKp& kp, float& ur) {
+    ur = kp.ur;
+    return ur >= 0;
+}
+
+// One point of the search pass: the best keypoint in the radius among octaves [level-1, level] of the
+// level grid (cs, ci) (strict-< first minimum from bestDist's initial value), optional Fuse stereo / mono
+// reprojection gate, optional "already matched" blocking. k_kf_search and k_fuse_batch both run this body.
+template <class Fr>
+__device__ __forceinline__ void kf_search_point(const Fr& fr, const int* cs, const int* ci, const KfProj& p,
+                                                const orbfe_map_point_3d& mp, float radius, int reproj,
+                                                const float* inv_sigma2, const int* blocked0, const int* first, int q,
+                                                int& bestIdx, int& bestDist) {
+    mt_for_area(fr, cs, ci, p.u, p.v, radius, -1, -1, [&](int idx, const auto& kp) {
+        if (blocked0 && (blocked0[idx] || first[idx] < q)) return;
+        if (reproj) {
+            const float ex = p.u - kp.x, ey = p.v - kp.y;
+            float kur;
+            if (kf_uright(fr, idx, kp, kur)) {
+                const float er = p.ur - kur;
+                const float e2 = ex * ex + ey * ey + er * er;
+                if ((double)(e2 * inv_sigma2[kp.octave]) > 7.8) return;
+            } else {
+                const float e2 = ex * ex + ey * ey;
+                if ((double)(e2 * inv_sigma2[kp.octave]) > 5.99) return;
+            }
+        }
+        const int dist = mt_hamming(mp.desc, fr.desc + 8 * idx);
+        if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
+    });
 }
 
 // Best keypoint in the radius among octaves [level-1, level] (strict-< first minimum), optional
@@ -195,25 +258,9 @@ __global__ __launch_bounds__(MT_NT) void k_kf_search(FrameDev fr, const KfProj* 
     int result = -1, bestIdx = -1, bestDist = init_best;
     if (p.level >= 0) {
         const float radius = th * fr.scale[p.level];
-        const orbfe_map_point_3d& mp = pts[q];
         // cell_off = MT_NCELL: a two-camera keyframe's right grid (GetFeaturesInArea(.., bRight), KeyFrame.cc:707-751)
-        mt_for_area(fr, fr.pcstart + p.level * fr.gstride_c + cell_off, fr.pcidx + p.level * fr.gstride_i, p.u, p.v, radius, -1,
-                    -1, [&](int idx, const OrbKeyPoint& kp) {
-            if (blocked0 && (blocked0[idx] || first[idx] < q)) return;
-            if (reproj) {
-                const float ex = p.u - kp.x, ey = p.v - kp.y;
-                if (fr.uright && fr.uright[idx] >= 0) {
-                    const float er = p.ur - fr.uright[idx];
-                    const float e2 = ex * ex + ey * ey + er * er;
-                    if ((double)(e2 * inv_sigma2[kp.octave]) > 7.8) return;
-                } else {
-                    const float e2 = ex * ex + ey * ey;
-                    if ((double)(e2 * inv_sigma2[kp.octave]) > 5.99) return;
-                }
-            }
-            const int dist = mt_hamming(mp.desc, fr.desc + 8 * idx);
-            if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
-        });
+        kf_search_point(fr, fr.pcstart + p.level * fr.gstride_c + cell_off, fr.pcidx + p.level * fr.gstride_i, p, pts[q],
+                        radius, reproj, inv_sigma2, blocked0, first, q, bestIdx, bestDist);
         if (bestIdx >= 0 && (float)bestDist <= max_acc) result = bestIdx;
     }
     if (out_dist) out_dist[q] = bestIdx >= 0 ? bestDist : -1;

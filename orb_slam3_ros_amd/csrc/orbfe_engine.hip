@@ -1556,3 +1556,6 @@ int orbfe_descriptor_distance(const uint8_t* a, const uint8_t* b) {
 
 // Batched SearchForTriangulation(KF1, KF2) over resident keyframes with geometry (LocalMapping::CreateNewMapPoints).
 #include "orbfe_tri_batch.hip"
+
+// Batched Fuse over resident keyframes with their search grids (LocalMapping::SearchInNeighbors, LoopClosing::SearchAndFuse).
+#include "orbfe_fuse_batch.hip"

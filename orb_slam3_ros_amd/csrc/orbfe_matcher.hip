@@ -133,8 +133,10 @@ __device__ __forceinline__ int mt_hamming(const uint8_t* a, const uint32_t* b) {
 }
 
 // Frame::GetFeaturesInArea (Frame.cc:657-723), calling f(idx) in the reference's order.
-template <typename Fn>
-__device__ __forceinline__ void mt_for_area(const FrameDev& fr, const int* cs, const int* ci, float x, float y, float r,
+// Fr: FrameDev, or any frame with its minx / miny / invw / invh and a keys[idx] record of x, y, octave
+// (KfGridFrame, a resident keyframe's geometry block).
+template <typename Fr, typename Fn>
+__device__ __forceinline__ void mt_for_area(const Fr& fr, const int* cs, const int* ci, float x, float y, float r,
                                             int minLevel, int maxLevel, Fn&& f) {
     const int nMinCellX = max(0, (int)floorf((x - fr.minx - r) * fr.invw));
     if (nMinCellX >= ORBFE_GRID_COLS) return;
@@ -151,7 +153,7 @@ __device__ __forceinline__ void mt_for_area(const FrameDev& fr, const int* cs, c
         const int j1 = cs[ix * ORBFE_GRID_ROWS + nMaxCellY + 1];
         for (int j = cs[ix * ORBFE_GRID_ROWS + nMinCellY]; j < j1; j++) {
             const int idx = ci[j];
-            const OrbKeyPoint kp = fr.keys[idx];
+            const auto kp = fr.keys[idx];
             if (bCheckLevels) {
                 if (kp.octave < minLevel) continue;
                 if (maxLevel >= 0 && kp.octave > maxLevel) continue;
@@ -4768,6 +4770,20 @@ struct orbfe_keyframe {
     int gvec = 0;              // its 16-byte words
     int nki = 0;               // entries of the FeatureVector
     std::vector<int32_t> offs; // has_geom: the CSR offsets on the host too (k_tri's item list is joined there)
+    // orbfe_keyframe_create_grid only (has_geom as well): a third allocation, what Fuse reads besides,
+    // [KfGridHdr | mvInvLevelSigma2 | cstart | cidx] at byte offsets 0, g_inv, g_cs, g_ci. cstart / cidx hold
+    // nlevels + 1 grids in FramePlan::plan_grid's layout (strides gstride_c = cells + 1 and gstride_i =
+    // max(n, 1); a two-camera keyframe's right cells at + MT_NCELL); grid 0, the full one, is not built.
+    bool has_grid = false;
+    int nleft = -1;            // two: NLeft
+    float minx = 0.f, maxx = 0.f, miny = 0.f, maxy = 0.f, mbf = 0.f;
+    uint8_t* grid = nullptr;   // has_grid && n > 0
+    int g_inv = 0, g_cs = 0, g_ci = 0, gstride_c = 0, gstride_i = 0;
+};
+// The head of a grid block: the keyframe's image bounds, cell sizes, mbf and NLeft (-1: one camera)
+struct KfGridHdr {
+    float minx, maxx, miny, maxy, invw, invh, mbf;
+    int nleft;
 };
 // 16-byte words of a geometry block, and of one of its level tables
 __host__ __device__ inline int kf_geom_lvec(int nlevels) { return (nlevels + 3) / 4; }
@@ -5130,9 +5146,10 @@ int orbfe_search_by_bow(const orbfe_keypoint* kf_keys, const uint8_t* kf_desc, c
 }  // extern "C"
 
 namespace {
-// orbfe_keyframe_create (level_sigma2 == NULL: the pack alone) and orbfe_keyframe_create_geom
+// orbfe_keyframe_create (level_sigma2 == NULL: the pack alone), orbfe_keyframe_create_geom and
+// orbfe_keyframe_create_grid (geom as well)
 int kf_create(const orbfe_frame* KF, const orbfe_feature_vector* fv, const float* level_sigma2, bool geom,
-              orbfe_keyframe** out) {
+              orbfe_keyframe** out, bool grid = false) {
     if (!out) return ORBFE_E_ARG;
     *out = nullptr;
     if (!KF || !fv || KF->n < 0 || fv->n_nodes < 0 || (KF->n > 0 && (!KF->keys || !KF->desc))) return ORBFE_E_ARG;
@@ -5143,6 +5160,10 @@ int kf_create(const orbfe_frame* KF, const orbfe_feature_vector* fv, const float
             for (int i = 0; i < n; i++)
                 if (KF->keys[i].octave < 0 || KF->keys[i].octave >= KF->nlevels) return ORBFE_E_ARG;
     }
+    // the grid's own refusals: bounds that give no cell size, more keypoints than k_mt_grid sorts, NLeft
+    if (grid && (!(KF->max_x > KF->min_x) || !(KF->max_y > KF->min_y) || KF->n > MT_GRID_MAXN ||
+                 (KF->two_cams && (KF->nleft < 0 || KF->nleft > KF->n))))
+        return ORBFE_E_ARG;
     bool repeats = false;   // an index in several nodes is accepted here and refused by the KF-KF search
     if (nn > 0 && (!fv_shape_ok(fv) || !fv_indices_unique(fv, n, &repeats))) return ORBFE_E_ARG;
     const int nki = nn > 0 ? fv->offsets[nn] : 0;
@@ -5161,6 +5182,12 @@ int kf_create(const orbfe_frame* KF, const orbfe_feature_vector* fv, const float
     kf->nlevels = geom ? KF->nlevels : 0;
     kf->nki = nki;
     if (geom && nn > 0) kf->offs.assign(fv->offsets, fv->offsets + nn + 1);
+    kf->has_grid = grid;
+    if (grid) {
+        kf->nleft = KF->two_cams ? KF->nleft : -1;
+        kf->minx = KF->min_x; kf->maxx = KF->max_x; kf->miny = KF->min_y; kf->maxy = KF->max_y;
+        kf->mbf = KF->mbf;
+    }
     if (n == 0) {   // nothing to match: no pack, every search gives the empty row
         *out = kf.release();
         return ORBFE_OK;
@@ -5188,7 +5215,7 @@ int kf_create(const orbfe_frame* KF, const orbfe_feature_vector* fv, const float
     struct Guard {
         uint8_t* p;
         ~Guard() { if (p) (void)hipFree(p); }
-    } guard{pack}, gguard{nullptr};
+    } guard{pack}, gguard{nullptr}, cguard{nullptr}, kguard{nullptr};
     HIPCHK(hipMemcpy(pack, h.data(), o_desc, hipMemcpyHostToDevice));
     // the geometry block: keypoint records, then mvScaleFactors and mvLevelSigma2
     uint8_t* gblk = nullptr;
@@ -5214,7 +5241,7 @@ int kf_create(const orbfe_frame* KF, const orbfe_feature_vector* fv, const float
             HIPCHK(hipMemcpyAsync(gblk + (size_t)n * 16, KF->scale_factors, (size_t)nlv * 4, hipMemcpyDeviceToDevice,
                                   nullptr));
         }
-        HIPCHK(hipStreamSynchronize(nullptr));
+        if (!grid) HIPCHK(hipStreamSynchronize(nullptr));
     } else {
         HIPCHK(hipMemcpy(pack + o_desc, KF->desc, (size_t)n * 32, hipMemcpyHostToDevice));
         if (geom) {
@@ -5229,9 +5256,48 @@ int kf_create(const orbfe_frame* KF, const orbfe_feature_vector* fv, const float
             HIPCHK(hipMemcpy(gblk, rec.data(), (size_t)n * 16, hipMemcpyHostToDevice));
         }
     }
+    // the grid block: the head and mvInvLevelSigma2 from the host, the level grids by k_mt_grid from the
+    // keypoint records (a host view's are uploaded for this launch only)
+    uint8_t* cblk = nullptr;
+    if (grid) {
+        const int cells = (KF->two_cams ? 2 : 1) * MT_NCELL, ngr = nlv + 1;
+        kf->gstride_c = cells + 1;
+        kf->gstride_i = std::max(n, 1);
+        kf->g_inv = (int)sizeof(KfGridHdr);
+        kf->g_cs = kf->g_inv + lvec * 16;
+        kf->g_ci = kf->g_cs + ngr * kf->gstride_c * 4;
+        const size_t gbytes = (size_t)kf->g_ci + (size_t)ngr * kf->gstride_i * 4;
+        HIPCHK(hipMalloc((void**)&cblk, gbytes));
+        cguard.p = cblk;
+        std::vector<uint8_t> head((size_t)kf->g_cs, 0);
+        const KfGridHdr hd{KF->min_x, KF->max_x, KF->min_y, KF->max_y,
+                           static_cast<float>(ORBFE_GRID_COLS) / (KF->max_x - KF->min_x),
+                           static_cast<float>(ORBFE_GRID_ROWS) / (KF->max_y - KF->min_y), KF->mbf, kf->nleft};
+        memcpy(head.data(), &hd, sizeof(hd));
+        float* inv = (float*)(head.data() + kf->g_inv);
+        for (int l = 0; l < nlv; l++) inv[l] = 1.0f / level_sigma2[l];   // KeyFrame's mvInvLevelSigma2
+        HIPCHK(hipMemcpy(cblk, head.data(), head.size(), hipMemcpyHostToDevice));
+        const OrbKeyPoint* dkeys = (const OrbKeyPoint*)KF->keys;
+        if (!KF->device) {
+            uint8_t* up = nullptr;
+            HIPCHK(hipMalloc((void**)&up, (size_t)n * sizeof(OrbKeyPoint)));
+            kguard.p = up;
+            HIPCHK(hipMemcpy(up, KF->keys, (size_t)n * sizeof(OrbKeyPoint), hipMemcpyHostToDevice));
+            dkeys = (const OrbKeyPoint*)up;
+        }
+        SbpInit none;
+        memset(&none, 0, sizeof(none));
+        hipLaunchKernelGGL(k_mt_grid, dim3(ngr - 1), dim3(1024), 0, nullptr, dkeys, n, kf->nleft, hd.minx, hd.miny, hd.invw,
+                           hd.invh, (int*)(cblk + kf->g_cs), (int*)(cblk + kf->g_ci), kf->gstride_c, kf->gstride_i, ngr,
+                           none, BandGrid{nullptr, nullptr, 0, 0}, 1);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(nullptr));
+    }
     guard.p = nullptr;
     gguard.p = nullptr;
+    cguard.p = nullptr;
     kf->pack = pack;
+    kf->grid = cblk;
     kf->geom = gblk;
     kf->gvec = geom ? gvec : 0;
     *out = kf.release();
@@ -5252,10 +5318,18 @@ int orbfe_keyframe_create_geom(const orbfe_frame* KF, const orbfe_feature_vector
 
 int orbfe_keyframe_has_geom(const orbfe_keyframe* kf) { return kf ? (kf->has_geom ? 1 : 0) : ORBFE_E_ARG; }
 
+int orbfe_keyframe_create_grid(const orbfe_frame* KF, const orbfe_feature_vector* fv, const float* level_sigma2,
+                               orbfe_keyframe** out) {
+    return kf_create(KF, fv, level_sigma2, true, out, true);
+}
+
+int orbfe_keyframe_has_grid(const orbfe_keyframe* kf) { return kf ? (kf->has_grid ? 1 : 0) : ORBFE_E_ARG; }
+
 void orbfe_keyframe_destroy(orbfe_keyframe* kf) {
     if (!kf) return;
     if (kf->pack) (void)hipFree(kf->pack);
     if (kf->geom) (void)hipFree(kf->geom);
+    if (kf->grid) (void)hipFree(kf->grid);
     delete kf;
 }
 

@@ -332,21 +332,25 @@ class KeyFrameFeatures:
     device. The arrays may be released after construction; close() (or the finaliser) frees the HBM
     copy and must not run while a search uses the object."""
 
-    def __init__(self, frame, featvec: FeatureVector, level_sigma2=None):
+    def __init__(self, frame, featvec: FeatureVector, level_sigma2=None, grid: bool = False):
         """level_sigma2 (mvLevelSigma2, one float per level of frame.scale_factors): the keyframe also keeps
         its geometry in HBM (keypoint positions, octaves, mvuRight, the level tables; orbfe_keyframe_create_geom)
-        and serves ORBmatcher.SearchForTriangulationBatch."""
+        and serves ORBmatcher.SearchForTriangulationBatch. grid (needs level_sigma2): it keeps its image
+        bounds, mvInvLevelSigma2 and level-restricted cell grids as well (orbfe_keyframe_create_grid) and
+        serves ORBmatcher.FuseBatch."""
         import weakref
         lib = _lib.load()
         h = ctypes.c_void_p()
         if level_sigma2 is None:
+            if grid:
+                raise ValueError("a keyframe with its grid needs level_sigma2")
             _lib.check(lib.orbfe_keyframe_create(frame.ref(), featvec.ref(), ctypes.byref(h)), "KeyFrameFeatures")
         else:
             sg = np.ascontiguousarray(level_sigma2, np.float32).reshape(-1)
             if len(sg) < int(frame.c.nlevels):
                 raise ValueError("level_sigma2 needs one entry per level")
-            _lib.check(lib.orbfe_keyframe_create_geom(frame.ref(), featvec.ref(), sg.ctypes.data, ctypes.byref(h)),
-                       "KeyFrameFeatures")
+            create = lib.orbfe_keyframe_create_grid if grid else lib.orbfe_keyframe_create_geom
+            _lib.check(create(frame.ref(), featvec.ref(), sg.ctypes.data, ctypes.byref(h)), "KeyFrameFeatures")
         self.handle = h.value
         self.N = int(lib.orbfe_keyframe_n(self.handle))
         self._fin = weakref.finalize(self, lib.orbfe_keyframe_destroy, self.handle)
@@ -357,10 +361,43 @@ class KeyFrameFeatures:
             raise ValueError("KeyFrameFeatures is closed")
         return bool(_lib.check(_lib.load().orbfe_keyframe_has_geom(self.handle), "has_geom"))
 
+    def has_grid(self) -> bool:
+        if self.handle is None:
+            raise ValueError("KeyFrameFeatures is closed")
+        return bool(_lib.check(_lib.load().orbfe_keyframe_has_grid(self.handle), "has_grid"))
+
     def close(self):
         if self.handle is not None:
             self._fin()
             self.handle = None
+
+
+class FuseJob(ctypes.Structure):
+    """struct orbfe_fuse_job: one (keyframe, pose) target of ORBmatcher.FuseBatch (120 bytes)."""
+    _fields_ = [("kf", ctypes.c_void_p), ("skip", ctypes.c_void_p), ("cam", KFCamera), ("model", CameraModel),
+                ("bRight", ctypes.c_int32)]
+
+    @staticmethod
+    def make(kf, cam: KFCamera = None, model: "CameraModel" = None, skip=None, bRight: bool = False):
+        """kf: KeyFrameFeatures(frame, featvec, level_sigma2, grid=True), or None: the keyframe is skipped (its
+        row is -1). cam / model / bRight as ORBmatcher.Fuse takes them (model None = pinhole from cam). skip:
+        one flag per point of the call, nonzero = not searched in this keyframe. The job keeps its skip array
+        and the keyframe alive; FuseBatch checks the array's length against its points."""
+        j = FuseJob()
+        j._kf = kf
+        j._skip = None
+        if kf is None:
+            return j
+        if kf.handle is None:
+            raise ValueError("KeyFrameFeatures is closed")
+        j.kf = kf.handle
+        j.cam = cam
+        j.model = model if model is not None else CameraModel.make("pinhole", cam.fx, cam.fy, cam.cx, cam.cy)
+        if skip is not None:
+            j._skip = np.ascontiguousarray(np.asarray(skip) != 0, np.uint8).reshape(-1)
+            j.skip = j._skip.ctypes.data if len(j._skip) else None
+        j.bRight = int(bool(bRight))
+        return j
 
 
 class TriJob(ctypes.Structure):
@@ -913,6 +950,39 @@ class ORBmatcher:
                                          int(bool(bRight)), bi.ctypes.data, bd.ctypes.data)
         n = _lib.check(n, "Fuse")
         return n, bi, bd
+
+    # the Fuse(pKFi, vpMapPointMatches) calls of LocalMapping::SearchInNeighbors (LocalMapping.cc:765-775) or
+    # the Fuse(pKF, Scw, vpPoints, 4, vpReplacePoints) calls of LoopClosing::SearchAndFuse in one call over
+    # resident keyframes with their grids
+    def FuseBatch(self, jobs, points3d, th=3.0, sim3=False):
+        """jobs: FuseJob per target keyframe; points3d: MAP_POINT_3D records shared by every job. Returns
+        (nfused int32 [J], best_idx int32 [J, n], best_dist int32 [J, n]); row c equals Fuse on keyframe c
+        with the points of jobs[c].skip flagged ORBFE_MP_SKIP."""
+        pts = _records(points3d, MAP_POINT_3D_DTYPE, "points3d")
+        J, n = len(jobs), len(pts)
+        arr = (FuseJob * max(J, 1))()
+        for c, j in enumerate(jobs):
+            if not isinstance(j, FuseJob):
+                raise ValueError("jobs must be FuseJob records")
+            if j._kf is not None and j._kf.handle is None:
+                raise ValueError("KeyFrameFeatures is closed")
+            if j._skip is not None and len(j._skip) != n:
+                raise ValueError(f"skip must hold one flag per point ({n})")
+            ctypes.memmove(ctypes.byref(arr, c * ctypes.sizeof(FuseJob)), ctypes.byref(j), ctypes.sizeof(FuseJob))
+        bi = np.full((J, n), -1, np.int32)
+        bd = np.full((J, n), -1, np.int32)
+        nf = np.zeros(J, np.int32)
+        if J:
+            _lib.check(self._lib.orbfe_fuse_batch(arr, J, pts.ctypes.data if n else None, n, float(th), int(bool(sim3)),
+                                                  bi.ctypes.data, bd.ctypes.data, nf.ctypes.data), "Fuse(batch)")
+        return nf, bi, bd
+
+    @staticmethod
+    def last_fuse_batch():
+        """(searched jobs, empty rows, workgroups) of this thread's last FuseBatch."""
+        w = np.zeros(3, np.int32)
+        _lib.check(_lib.load().orbfe_matcher_last_fuse_batch(w.ctypes.data), "last_fuse_batch")
+        return tuple(int(v) for v in w)
 
     # SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (:427-523) and the
     # vpPointsKFs / vpMatchedKF overload (:525-646)

@@ -71,13 +71,20 @@ struct KeyFrameCache {
         kf.nlevels = pKF->mnScaleLevels;
         kf.scale_factors = pKF->mvScaleFactors.data();
         kf.two_cams = pKF->mpCamera2 ? 1 : 0;
+        // and what Fuse reads besides (FuseNeighbours_orbfe): the image bounds, mbf and NLeft
+        kf.min_x = pKF->mnMinX; kf.max_x = pKF->mnMaxX; kf.min_y = pKF->mnMinY; kf.max_y = pKF->mnMaxY;
+        kf.mbf = pKF->mbf;
+        kf.nleft = pKF->mpCamera2 ? pKF->NLeft : 0;
         vector<uint32_t> ids, idx;
         vector<int32_t> off;
         flatten(pKF->mFeatVec, ids, off, idx);
         const orbfe_feature_vector fv{(int32_t)ids.size(), ids.data(), off.data(), idx.data()};
         orbfe_keyframe* h = nullptr;
         if ((int)pKF->mvLevelSigma2.size() < kf.nlevels) return nullptr;
-        if (orbfe_keyframe_create_geom(&kf, &fv, pKF->mvLevelSigma2.data(), &h) != ORBFE_OK) return nullptr;
+        // with its search grid; a keyframe the grid refuses (more than 8,192 features) keeps its geometry
+        if (orbfe_keyframe_create_grid(&kf, &fv, pKF->mvLevelSigma2.data(), &h) != ORBFE_OK &&
+            orbfe_keyframe_create_geom(&kf, &fv, pKF->mvLevelSigma2.data(), &h) != ORBFE_OK)
+            return nullptr;
         lock_guard<mutex> lk(mu);
         auto ins = map.emplace(pKF, h);
         if (!ins.second) {   // another thread created it meanwhile
