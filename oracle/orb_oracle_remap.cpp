@@ -25,7 +25,7 @@ short sat_short(float v) {
 }
 int sat_int(float v) {
     if (v >= 2147483520.f) return INT_MAX;
-    if (v <= -2147483648.f) return INT_MIN;
+    if (!(v > -2147483648.f)) return INT_MIN;   // NaN too: cvtss2si's result (lrint(NaN) is unspecified)
     return cv_round(v);
 }
 

@@ -21,9 +21,10 @@ struct RemapPx {
 };
 __device__ __forceinline__ RemapPx remap_setup(int sw, int sh, int sstride, float mx, float my) {
     const float fxs = mx * 32.f, fys = my * 32.f;
-    // saturate_cast<int>(float): round half to even, saturating
-    const int X = fxs >= 2147483520.f ? INT_MAX : (fxs <= -2147483648.f ? INT_MIN : __float2int_rn(fxs));
-    const int Y = fys >= 2147483520.f ? INT_MAX : (fys <= -2147483648.f ? INT_MIN : __float2int_rn(fys));
+    // saturate_cast<int>(float): round half to even, saturating; NaN fails the second comparison
+    // and becomes INT_MIN as cvtss2si makes it (the footprint is outside: the pixel is 0)
+    const int X = fxs >= 2147483520.f ? INT_MAX : (!(fxs > -2147483648.f) ? INT_MIN : __float2int_rn(fxs));
+    const int Y = fys >= 2147483520.f ? INT_MAX : (!(fys > -2147483648.f) ? INT_MIN : __float2int_rn(fys));
     const int sx = min(max(X >> 5, -32768), 32767), sy = min(max(Y >> 5, -32768), 32767);
     const int ax = X & 31, ay = Y & 31;
     uint32_t w0, w1, w2, w3;
