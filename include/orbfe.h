@@ -999,7 +999,11 @@ int orbfe_vocabulary_info(const orbfe_vocabulary* voc, int32_t* k, int32_t* L, i
 /* transform(features, BowVector& v, FeatureVector& fv, levelsup) (TemplatedVocabulary.h:1139-1198,
  * :1218-1262) for n descriptors (n x 32 bytes). Outputs (capacity n each, fv_offsets n + 1):
  * BowVector as ascending word ids + weights (*bow_n entries), FeatureVector as ascending node ids
- * with offsets into fv_indices (*fv_n nodes). Returns 0. */
+ * with offsets into fv_indices (*fv_n nodes). Returns 0. n <= 4096; above, ORBFE_E_CAPACITY and no
+ * output, the counts included, is written. A childless node is a leaf whether or not its isLeaf flag
+ * is set (word id 0 without it, as Node()). A feature whose leaf lies above level L - levelsup is
+ * listed under node 0: the reference leaves its `nid` uninitialised there, 0 is this library's rule
+ * (all forms below share it). */
 int orbfe_vocabulary_transform(const orbfe_vocabulary* voc, const uint8_t* desc, int32_t n, int32_t levelsup,
                                uint32_t* bow_word_ids, double* bow_weights, int32_t* bow_n,
                                uint32_t* fv_node_ids, int32_t* fv_offsets, uint32_t* fv_indices, int32_t* fv_n);
@@ -1032,7 +1036,7 @@ int orbfe_vocabulary_transform_batch(const orbfe_vocabulary* voc, const uint8_t*
 
 /* Frame::ComputeBoW for one frame (the Tracking thread's call): F is a host view or the view of
  * orbfe_frame_device_view, whose descriptors are read in HBM; only F->n, F->desc and F->device are
- * read. F->n <= 8192 (ORBFE_E_CAPACITY above). Host outputs as orbfe_vocabulary_transform's. One host
+ * read. F->n <= 8192 (ORBFE_E_CAPACITY above, no output written). Host outputs as orbfe_vocabulary_transform's. One host
  * wait: the result comes back as one block. */
 int orbfe_frame_compute_bow(const orbfe_vocabulary* voc, const orbfe_frame* F, int32_t levelsup,
                             uint32_t* bow_word_ids, double* bow_weights, int32_t* bow_n,

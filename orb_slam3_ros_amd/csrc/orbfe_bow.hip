@@ -254,11 +254,11 @@ int orbfe_vocabulary_transform(const orbfe_vocabulary* voc, const uint8_t* desc,
     if (!voc || n < 0 || (n > 0 && (!desc || !bow_word_ids || !bow_weights || !fv_node_ids || !fv_indices)) ||
         !bow_n || !fv_n || !fv_offsets)
         return ORBFE_E_ARG;
+    if (voc->n_words != 0 && n > BOW_MAXN) return ORBFE_E_CAPACITY;   // refused before any output is written
     *bow_n = 0;
     *fv_n = 0;
     fv_offsets[0] = 0;
     if (voc->n_words == 0 || n == 0) return ORBFE_OK;   // empty(): v and fv cleared
-    if (n > BOW_MAXN) return ORBFE_E_CAPACITY;
     int dev = 0;
     HIPCHK(hipGetDevice(&dev));
     if (dev != voc->device) return ORBFE_E_ARG;

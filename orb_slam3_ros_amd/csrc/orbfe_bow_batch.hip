@@ -296,11 +296,11 @@ int orbfe_frame_compute_bow(const orbfe_vocabulary* voc, const orbfe_frame* F, i
         !fv_offsets)
         return ORBFE_E_ARG;
     const int n = F->n;
+    if (voc->n_words != 0 && n > BB_MAXN) return ORBFE_E_CAPACITY;   // refused before any output is written
     *bow_n = 0;
     *fv_n = 0;
     fv_offsets[0] = 0;
     if (voc->n_words == 0 || n == 0) return ORBFE_OK;   // empty(): v and fv cleared
-    if (n > BB_MAXN) return ORBFE_E_CAPACITY;
     if (F->device && ((uintptr_t)F->desc & 3)) return ORBFE_E_ARG;
     int dev = 0;
     HIPCHK(hipGetDevice(&dev));
