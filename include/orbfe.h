@@ -1254,6 +1254,10 @@ enum {
 };
 int orbfe_matcher_last_bow_form(void);
 int orbfe_matcher_last_bow_batch(int32_t* out);
+/* Of this thread's last batched fisheye kNN launch (orbfe_stereo_knn_batch, orbfe_stereo_knn_slabs, the
+ * one-frame fisheye Frame): out[0] = W of the k_knn2_batch<W> that ran (16 below 16 frames, else 4), out[1]
+ * = its dynamic LDS bytes (cap * 32). Both 0 before the thread's first launch. A host record. */
+int orbfe_matcher_last_knn_form(int32_t* out);
 /* The same three counts for this thread's last orbfe_search_by_bow_kf_batch: out[0] matched in
  * k_bow_kfkf_batch's one workgroup, out[1] got the empty row (NULL, no features or FeatureVector on
  * either side, no node shared with KF1, or a call that returned before any launch), out[2] took

@@ -119,6 +119,7 @@ _SIGS = {
     "orbfe_matcher_last_form": (_c_int, []),
     "orbfe_matcher_last_bow_form": (_c_int, []),
     "orbfe_matcher_last_bow_batch": (_c_int, [_vp]),
+    "orbfe_matcher_last_knn_form": (_c_int, [_vp]),
     "orbfe_matcher_last_sim3_passes": (_c_int, []),
     "orbfe_undistort_points": (_c_int, [_vp, _c_int, _vp, _vp, _c_int, _vp]),
     "orbfe_remap_linear": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _vp, _c_int]),

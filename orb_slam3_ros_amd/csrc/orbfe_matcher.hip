@@ -3652,6 +3652,8 @@ thread_local int t_last_form = ORBFE_SBP_FORM_NONE;
 // orbfe_matcher_last_bow_form / _last_bow_batch: the same for the thread's last SearchByBoW call
 thread_local int t_bow_form = ORBFE_BOW_FORM_NONE;
 thread_local int t_bow_batch[3] = {0, 0, 0};   // one workgroup, empty row, multi-launch
+// orbfe_matcher_last_knn_form: W and the dynamic LDS bytes of the thread's last k_knn2_batch<W> launch
+thread_local int t_knn_form[2] = {0, 0};
 thread_local float t_last_ms = -1.f;
 thread_local hipEvent_t t_ev[2] = {nullptr, nullptr};
 struct MsTimer {
@@ -5477,6 +5479,8 @@ static void knn2_batch_launch(const StereoSide& SL, const StereoSide& SR, int ca
                               int32_t* d_l2r, int32_t* d_dist, int32_t* d_ngood, hipStream_t s) {
     const size_t lds = (size_t)cap * 32;
     const dim3 grid((cap + KNN_Q - 1) / KNN_Q, nframes);
+    t_knn_form[0] = nframes < 16 ? 16 : 4;
+    t_knn_form[1] = (int)lds;
     if (nframes < 16)   // a few frames: the whole CU on each block's 64 queries
         hipLaunchKernelGGL(k_knn2_batch<16>, grid, dim3(1024), lds, s, SL, SR, cap, ratio, (int*)d_l2r, (int*)d_dist,
                            (int*)d_ngood);
@@ -5679,6 +5683,13 @@ int orbfe_matcher_last_bow_form(void) { return t_bow_form; }
 int orbfe_matcher_last_bow_batch(int32_t* out) {
     if (!out) return ORBFE_E_ARG;
     for (int i = 0; i < 3; i++) out[i] = t_bow_batch[i];
+    return ORBFE_OK;
+}
+
+int orbfe_matcher_last_knn_form(int32_t* out) {
+    if (!out) return ORBFE_E_ARG;
+    out[0] = t_knn_form[0];
+    out[1] = t_knn_form[1];
     return ORBFE_OK;
 }
 
