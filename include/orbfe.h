@@ -1301,6 +1301,29 @@ int orbfe_matcher_last_sim3_passes(void);
  * Returns the element count. */
 int orbfe_debug_copy(orbfe_extractor* h, int what, int image, int level, void* dst, int cap_bytes);
 
+/* Debug/inspection (tests only): fill, with the 32-bit `word`, every buffer of the handle that the
+ * next call has to define for itself before it reads it, so that a test controls what a call finds
+ * in reused scratch. Device: the pyramid, the per-cell FAST keys and counts, the octree's level keys,
+ * node ids, output keys, level info and ranks, the output block {counts | keypoints | descriptors},
+ * the host API's image staging, the stereo results {nmatch | uR | depth} and SAD distances, and the
+ * RGB-D results and depth staging. Host: the pinned staging block. Left alone, because they persist
+ * by design: the resize / tile / scale tables, the image and depth pointer tables (their cache against
+ * the last call's pointers is part of the contract) and caller-owned outputs. Runs under the
+ * handle's lock after a device synchronisation, on the handle's own stream, and synchronises before it
+ * returns; a size that is no multiple of 4 keeps its tail bytes. The last frame's device view
+ * (orbfe_frame_device_view) is overwritten. *bytes_out (may be NULL) receives the bytes filled.
+ * Returns ORBFE_E_ARG for a NULL handle; ORBFE_OK with 0 bytes, and no device call, for a handle that
+ * has not allocated yet. */
+int orbfe_debug_fill_extractor(orbfe_extractor* h, uint32_t word, int64_t* bytes_out);
+
+/* Debug/inspection (tests only): the same for the calling thread's matcher scratch, ordered behind
+ * the thread's last device-resident search: the whole device arena, the whole mapped pinned
+ * staging block and the whole mapped slot block, bytes_out = {arena, staging, slots}. The status
+ * words (compared against the call sequence number), the multi-pass generation tags (zeroed once by
+ * design) and every host-side field (pass hints, sequence number) are not touched. ORBFE_OK with
+ * {0, 0, 0}, and no device call, on a thread that has made no matcher call; ORBFE_E_ARG for NULL. */
+int orbfe_debug_fill_matcher(uint32_t word, int64_t bytes_out[3]);
+
 /* Test hook: sort n <= 4096 u64 values by their high 32 bits with the device's block-parallel
  * replica of libstdc++ std::sort (used by DistributeOctTree); result must equal std::sort. */
 int orbfe_debug_block_sort(uint64_t* data, int n);

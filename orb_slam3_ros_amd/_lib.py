@@ -81,6 +81,8 @@ _SIGS = {
                                      _vp, _vp, _c_int, _P_int, _P_int, _vp, _vp, _c_int, _P_int, _P_int, _vp, _vp]),
     "orbfe_descriptor_distance": (_c_int, [_vp, _vp]),
     "orbfe_debug_copy": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _c_int]),
+    "orbfe_debug_fill_extractor": (_c_int, [_vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int64)]),
+    "orbfe_debug_fill_matcher": (_c_int, [ctypes.c_uint32, ctypes.POINTER(ctypes.c_int64)]),
     "orbfe_debug_block_sort": (_c_int, [_vp, _c_int]),
     "orbfe_version": (ctypes.c_char_p, []),
     "orbfe_search_by_projection_local": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_float, _c_int, _c_float, _c_float]),

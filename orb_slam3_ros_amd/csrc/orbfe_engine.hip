@@ -1471,6 +1471,56 @@ int orbfe_debug_copy(orbfe_extractor* h, int what, int image, int level, void* d
     return count;
 }
 
+int orbfe_debug_fill_extractor(orbfe_extractor* h, uint32_t word, int64_t* bytes_out) {
+    if (bytes_out) *bytes_out = 0;
+    if (!h) return ORBFE_E_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    std::lock_guard<std::mutex> lks(h->mu_stereo);   // d_sdist (orbfe_stereo_match_batch)
+    const OrbGeom& g = h->g;
+    const size_t B = (size_t)h->cap_b;
+    size_t o_kps = 0, o_desc = 0, o_end = 0;
+    if (h->cap_b) out_layout(h->cap_b, g.kp_cap, &o_kps, &o_desc, &o_end);
+    auto a16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    // every buffer a call must define for itself before it reads it, with the bytes it was allocated
+    // with (ensure, frame_pair, orbfe_stereo_match(_batch), orbfe_frame_rgbd); the tables (d_tab,
+    // d_ptile, d_scale, d_oct_ts) and the cached pointer tables (d_ptrs, d_rg_ptrs) stay
+    const struct { void* p; size_t bytes; } dev[] = {
+        {h->d_pyr, B * g.pyr_bytes},
+        {h->d_cellkeys, B * g.cellkeys_per_img * 4},
+        {h->d_cellcnt, B * g.total_cells * 4},
+        {h->d_lkeys, B * g.cellkeys_per_img * 4},
+        {h->d_nodeof, B * g.cellkeys_per_img * 2},
+        {h->d_outkeys, B * g.out_per_img * 4},
+        {h->d_lvinfo, B * g.nlevels * 4 * 4},
+        {h->d_ranks, B * g.out_per_img * 4},
+        {h->d_out, o_end},
+        {h->d_stage, h->stage_bytes},
+        {h->d_st, 16 + (size_t)h->stereo_kp * 8},
+        {h->d_sdist, (size_t)h->sdist_frames * h->sdist_kp * 4},
+        {h->d_rg, a16(a16((size_t)h->rg_kp * sizeof(OrbKeyPoint)) + (size_t)h->rg_kp * 8)},
+        {h->d_rg_stage, h->rg_stage_bytes},
+    };
+    int64_t total = 0;
+    bool any = h->h_pin != nullptr;
+    for (const auto& b : dev) any = any || (b.p && b.bytes >= 4);
+    if (!any) return ORBFE_OK;   // a handle that has never allocated: no device call
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipDeviceSynchronize());   // batch calls on a caller's stream may still be writing
+    hipStream_t s = h->own_stream;
+    for (const auto& b : dev) {
+        if (!b.p || b.bytes < 4) continue;
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)b.p, (int)word, b.bytes / 4, s));
+        total += (int64_t)(b.bytes / 4 * 4);
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    if (h->h_pin) {   // no device work reads or writes it between calls (every host call synchronised)
+        std::fill_n((uint32_t*)h->h_pin, h->pin_bytes / 4, word);
+        total += (int64_t)(h->pin_bytes / 4 * 4);
+    }
+    if (bytes_out) *bytes_out = total;
+    return ORBFE_OK;
+}
+
 #if ORBFE_OCT_STAMPS
 // diagnostic builds: the per-wave stamps of the last block sort of block (0, 0)
 int orbfe_debug_sort_stamps(uint64_t* out) {

@@ -5695,4 +5695,33 @@ int orbfe_matcher_last_knn_form(int32_t* out) {
 
 float orbfe_matcher_last_ms(void) { return t_last_ms; }
 
+int orbfe_debug_fill_matcher(uint32_t word, int64_t bytes_out[3]) {
+    if (!bytes_out) return ORBFE_E_ARG;
+    bytes_out[0] = bytes_out[1] = bytes_out[2] = 0;
+    MatchScratch& m = t_ms;
+    if (m.device < 0 || !m.stream) return ORBFE_OK;   // no matcher call on this thread yet: no device call
+    // behind the thread's last device-resident search (MatchScratch::tail), then drained: nothing
+    // reads or writes the three blocks while the host fills the mapped ones. hs (compared against
+    // seq), mbuf (generation tags) and every host field stay as they are.
+    int cur = 0;
+    HIPCHK(hipGetDevice(&cur));
+    if (cur != m.device) HIPCHK(hipSetDevice(m.device));   // the scratch belongs to the device of the thread's last call
+    HIPCHK(ms_after_tail(m.stream));
+    if (m.d && m.dcap >= 4) {
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)m.d, (int)word, m.dcap / 4, m.stream));
+        bytes_out[0] = (int64_t)(m.dcap / 4 * 4);
+    }
+    HIPCHK(hipStreamSynchronize(m.stream));
+    if (m.h) {
+        std::fill_n((uint32_t*)m.h, m.hcap / 4, word);
+        bytes_out[1] = (int64_t)(m.hcap / 4 * 4);
+    }
+    if (m.ho) {   // ocap counts 32-bit words
+        std::fill_n((uint32_t*)m.ho, m.ocap, word);
+        bytes_out[2] = (int64_t)m.ocap * 4;
+    }
+    if (cur != m.device) HIPCHK(hipSetDevice(cur));
+    return ORBFE_OK;
+}
+
 }  // extern "C"
