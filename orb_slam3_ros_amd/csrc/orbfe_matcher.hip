@@ -1064,24 +1064,111 @@ __device__ __forceinline__ void blk_enum(const BlkQuery& Q, const BlkGeom& gm, c
         }
     }
 }
+// The two packed forms of a candidate, in one place: blk_enum's 64-bit window key (dist << 40 |
+// rank << 4 | octave, the rank's low 13 bits the keypoint index; ~0: none) and the 32-bit entry of a
+// kept list (idx | octave << 13 | dist << 16; 0xFFFFFFFF: none). No candidate decodes as {-1, 256, -1}.
+struct BlkCand {
+    int idx, dist, octave;
+};
+struct BlkKey {
+    static constexpr unsigned long long kNone = ~0ull;
+    static constexpr uint32_t kNoEntry = 0xFFFFFFFFu;
+    static __device__ __forceinline__ BlkCand of_key(unsigned long long k) {
+        if (k == kNone) return {-1, 256, -1};
+        return {(int)((k >> 4) & 0x1FFFu), (int)(k >> 40), (int)(k & 15)};
+    }
+    static __device__ __forceinline__ int entry_idx(uint32_t e) { return (int)(e & 0x1FFFu); }
+    static __device__ __forceinline__ BlkCand of_entry(uint32_t e) {
+        if (e == kNoEntry) return {-1, 256, -1};
+        return {entry_idx(e), (int)(e >> 16), (int)((e >> 13) & 7)};
+    }
+    static __device__ __forceinline__ uint32_t entry(unsigned long long k) {
+        return k == kNone ? kNoEntry
+                          : (uint32_t)((k >> 4) & 0x1FFFu) | (uint32_t)((k & 15) << 13) | (uint32_t)((k >> 40) << 16);
+    }
+};
+// The first NEED (1 or 2) entries of a query's sorted list L that gate(idx) leaves free: the LEN gate
+// reads issued together, the selection by selects in registers. A list that runs out while the window
+// holds more candidates (cnt > LEN) is enumerated again (exact, rare): rescan(f) runs blk_enum over the
+// query's window with f(key, idx), and the same gate picks the two smallest keys. b1 / b2: best, second.
+struct BlkPick {
+    BlkCand b1, b2;
+};
+template <int NEED, int LEN, typename Gate, typename Rescan>
+__device__ __forceinline__ BlkPick blk_pick(const uint32_t (&L)[LEN], int cnt, Gate&& gate, Rescan&& rescan) {
+    bool free_[LEN];
+#pragma unroll
+    for (int k = 0; k < LEN; k++) free_[k] = L[k] != BlkKey::kNoEntry && gate(BlkKey::entry_idx(L[k]));
+    uint32_t e1 = BlkKey::kNoEntry, e2 = BlkKey::kNoEntry;
+#pragma unroll
+    for (int k = LEN - 1; k >= 0; k--) {   // from the far end: e1 ends as the first free entry, e2 as the second
+        e2 = free_[k] ? e1 : e2;
+        e1 = free_[k] ? L[k] : e1;
+    }
+    if ((NEED == 2 ? e2 : e1) == BlkKey::kNoEntry && cnt > LEN) {
+        unsigned long long k1 = BlkKey::kNone, k2 = BlkKey::kNone;
+        rescan([&](unsigned long long key, int idx) {
+            if (!gate(idx)) return;
+            const bool lt1 = key < k1, lt2 = key < k2;   // selects, not a store through a chosen pointer
+            k2 = lt1 ? k1 : (lt2 ? key : k2);
+            k1 = lt1 ? key : k1;
+        });
+        return {BlkKey::of_key(k1), BlkKey::of_key(k2)};
+    }
+    return {BlkKey::of_entry(e1), BlkKey::of_entry(e2)};
+}
 // the reference's acceptance from the best / second-best (dist, octave) of a query
 template <int MODE>
-__device__ __forceinline__ int blk_accept(int bestIdx, int bestDist, int bestLevel, int bestDist2, int bestLevel2,
-                                          float nnratio, int maxDist) {
-    if (bestIdx < 0) return -1;
+__device__ __forceinline__ int blk_accept(const BlkCand& b1, const BlkCand& b2, float nnratio, int maxDist) {
+    if (b1.idx < 0) return -1;
     if (MODE == 0)
-        return bestDist <= MT_TH_HIGH && !(bestLevel == bestLevel2 && bestDist > nnratio * bestDist2) ? bestIdx : -1;
-    return bestDist <= maxDist ? bestIdx : -1;
+        return b1.dist <= MT_TH_HIGH && !(b1.octave == b2.octave && b1.dist > nnratio * b2.dist) ? b1.idx : -1;
+    return b1.dist <= maxDist ? b1.idx : -1;
 }
 
 #define MT_BLK_LIST 8   // candidates kept per query: the smallest keys, as u32 idx | octave << 13 | dist << 16
 // Bucket bounds region: 4 zero words, then one counter per bucket padded to a multiple of 4 NT (each
 // thread scans a run of whole int4s); after the placement, word 4 + c = end of bucket c, so the
 // enumeration's bounds array ("be", be[c] = start of c, be[c + 1] = end) is region + 3.
-__host__ __device__ __forceinline__ int blk_be_words(int nbk, int nt) {
-    const int per = ((nbk + nt - 1) / nt + 3) & ~3;
-    return per * nt + 4;
-}
+__host__ __device__ constexpr int blk_be_words(int nbk, int nt) { return (((nbk + nt - 1) / nt + 3) & ~3) * nt + 4; }
+// The dynamic LDS of the one-workgroup kernels, host (byte counts) and device (pointers) from one
+// description. Every variant: keypoints {x, y, rank bits, uR} and descriptors (2 x uint4) by bucket
+// position, the bucket bounds region (blk_be_words; be = region + 3); then, by keypoint index,
+//   BLK_ONE / BLK_TWO_LAST: two first[] states (then the commit's slots), angles, blocked flags
+//   BLK_TWO_LOCAL: writers per slot (then the commit's slots), MT_B4_WCAP writer entries
+//                  (entry << 1 | Observations() > 0), the l2r / r2l partner, blocked flags
+//   BLK_MULTI0: blocked flags.
+// n keypoints, nbk buckets over all cameras.
+#define MT_B4_WCAP 6
+enum BlkVar { BLK_ONE, BLK_TWO_LAST, BLK_TWO_LOCAL, BLK_MULTI0 };
+struct BlkLds {
+    int n, nbe, var;
+    __host__ __device__ constexpr BlkLds(int n_, int nbk, int var_)
+        : n(n_), nbe(blk_be_words(nbk, MT_BLK_NT)), var(var_) {}
+    __host__ __device__ static constexpr int state_bytes(int var) {   // per keypoint, after the bounds region
+        return var == BLK_MULTI0 ? 0 : var == BLK_TWO_LOCAL ? 4 + 2 * MT_B4_WCAP + 2 : 2 * 4 + 4;
+    }
+    __host__ __device__ static constexpr int bytes_per_kp(int var) { return 16 + 32 + state_bytes(var) + 1; }
+    __host__ __device__ constexpr size_t o_ber() const { return (size_t)n * 48; }
+    __host__ __device__ constexpr size_t o_state() const { return o_ber() + (size_t)nbe * 4; }
+    __host__ __device__ constexpr size_t o_blk() const { return o_state() + (size_t)n * state_bytes(var); }
+    __host__ __device__ constexpr size_t bytes() const { return o_blk() + (size_t)n + 16; }
+    __device__ float4* kp(uint8_t* sm) const { return (float4*)sm; }
+    __device__ uint4* desc(uint8_t* sm) const { return (uint4*)(sm + (size_t)n * 16); }
+    __device__ int* ber(uint8_t* sm) const { return (int*)(sm + o_ber()); }
+    __device__ int* first(uint8_t* sm) const { return (int*)(sm + o_state()); }                 // BLK_ONE / BLK_TWO_LAST
+    __device__ float* ang(uint8_t* sm) const { return (float*)(first(sm) + 2 * n); }
+    __device__ int* wcnt(uint8_t* sm) const { return (int*)(sm + o_state()); }                  // BLK_TWO_LOCAL
+    __device__ uint16_t* wl(uint8_t* sm) const { return (uint16_t*)(wcnt(sm) + n); }
+    __device__ int16_t* link(uint8_t* sm) const { return (int16_t*)(wl(sm) + (size_t)MT_B4_WCAP * n); }
+    __device__ uint8_t* blk(uint8_t* sm) const { return sm + o_blk(); }
+};
+// the byte counts the launches have always requested, region by region
+static_assert(BlkLds(1000, 300, BLK_ONE).bytes() == 1000 * (16 + 32 + 8 + 4 + 1) + blk_be_words(300, MT_BLK_NT) * 4 + 16, "");
+static_assert(BlkLds(1000, 600, BLK_TWO_LAST).bytes() == BlkLds(1000, 600, BLK_ONE).bytes(), "");
+static_assert(BlkLds(1000, 600, BLK_TWO_LOCAL).bytes() ==
+                  1000 * (16 + 32 + 4 + 2 * MT_B4_WCAP + 2 + 1) + blk_be_words(600, MT_BLK_NT) * 4 + 16, "");
+static_assert(BlkLds(1000, 300, BLK_MULTI0).bytes() == 1000 * (16 + 32 + 1) + blk_be_words(300, MT_BLK_NT) * 4 + 16, "");
 // k_sbp_block's / k_sbp_multi0's LDS frame: the (octave, band, strip) bucket index (counts, scan,
 // placement; the order inside a bucket is irrelevant: every candidate carries its enumeration rank),
 // keypoints {x, y, rank bits, uR} and descriptors by bucket position, blocked flags (and angles, the
@@ -1213,11 +1300,87 @@ __device__ __forceinline__ int blk_list(const BlkQuery& Q, const BlkGeom& gm, co
         }
     }, cbase, nwin);
 #pragma unroll
-    for (int k = 0; k < LEN; k++)
-        L[k] = K[k] == ~0ull ? 0xFFFFFFFFu
-                             : (uint32_t)((K[k] >> 4) & 0x1FFFu) | (uint32_t)((K[k] & 15) << 13) |
-                                   (uint32_t)((K[k] >> 40) << 16);
+    for (int k = 0; k < LEN; k++) L[k] = BlkKey::entry(K[k]);
     return c;
+}
+// one LDS atomic per wave and distinct bin (the assignments of a frame fall in a few bins: same-address
+// atomics from every lane serialise); b < 0: this lane adds nothing
+__device__ __forceinline__ void mt_hist_add_wave(int b, int* s_hist) {
+    for (unsigned long long act = __ballot(b >= 0); act; act = __ballot(b >= 0)) {
+        const int lead = __builtin_amdgcn_readlane(b, (int)__builtin_ctzll(act));
+        const unsigned long long same = __ballot(b == lead);
+        if ((threadIdx.x & 63) == (int)__builtin_ctzll(same)) atomicAdd(&s_hist[lead], (int)__popcll(same));
+        if (b == lead) b = -1;
+    }
+}
+// The in-block commit of the one-workgroup searches (k_mt_commit_count / _drop / _write in one block)
+// over the thread's EPT entries: the last writer of a slot wins and, ROT, every assignment enters the
+// rotation histogram, ComputeThreeMaxima's dropped bins clear their slots and count once per entry
+// (ORBmatcher.cc:1775-1792,1864-1884). Entry j: res(j) its slot (< 0: none), ent(j) its position in
+// the reference's sequential run, handle(j) the id it stores, angle(j) its query-side angle. live =
+// false (k_sbp_block4 gave up) writes and counts nothing. LDS: slots[n] (dead search state), the
+// keypoint angles, hist[MT_HISTO] and cnt[] zeroed by the caller before its last barrier, keep.
+// Ends with every wave's stores complete and a barrier; cnt = {writes, dropped (ROT)} for the caller
+// to publish.
+struct BlkCommitLds {
+    int* slots;
+    const float* ang;
+    int* hist;
+    unsigned* keep;
+    int* cnt;
+};
+template <int EPT, bool ROT, typename Res, typename Ent, typename Handle, typename Angle>
+__device__ __forceinline__ void blk_commit(int n, bool live, const BlkIO& io, unsigned long long npair,
+                                           const BlkCommitLds& s, Res&& res, Ent&& ent, Handle&& handle,
+                                           Angle&& angle) {
+    const int tid = threadIdx.x;
+    for (int k = tid; k < n; k += MT_BLK_NT) s.slots[k] = -1;
+    SYNC();
+    int nas = 0;
+    int bins[EPT];
+#pragma unroll
+    for (int j = 0; j < EPT; j++) {
+        bins[j] = -1;
+        if (!live || res(j) < 0) continue;
+        atomicMax(&s.slots[res(j)], ent(j));
+        nas++;
+        if (ROT && io.checkOri) bins[j] = mt_rot_bin(angle(j), s.ang[res(j)]);
+    }
+    nas = wave_sum_dpp(nas);
+    if ((tid & 63) == 0 && nas) atomicAdd(&s.cnt[0], nas);
+    if (ROT && io.checkOri) {
+#pragma unroll
+        for (int j = 0; j < EPT; j++) mt_hist_add_wave(bins[j], s.hist);
+    }
+    SYNC();
+    if (ROT) {
+        if (tid == 0) *s.keep = io.checkOri ? mt_three_maxima_keep(s.hist) : 0xFFFFFFFFu;
+        SYNC();
+        int ndrop = 0;
+#pragma unroll
+        for (int j = 0; j < EPT; j++) {
+            if (res(j) < 0 || bins[j] < 0 || ((*s.keep >> bins[j]) & 1u)) continue;
+            s.slots[res(j)] = -2;
+            io.mvp_out[res(j)] = -1;
+            ndrop++;
+        }
+        ndrop = wave_sum_dpp(ndrop);
+        if ((tid & 63) == 0 && ndrop) atomicAdd(&s.cnt[1], ndrop);
+        SYNC();
+    }
+    // the last writer of each slot that no dropped entry cleared stores its record's id
+#pragma unroll
+    for (int j = 0; j < EPT; j++)
+        if (live && res(j) >= 0 && s.slots[res(j)] == ent(j)) io.mvp_out[res(j)] = handle(j);
+    if (io.stats && npair) {
+        atomicAdd(&io.stats[0], npair);
+        atomicAdd(&io.stats[1], npair);
+    }
+    // every wave's slot writes complete (vmcnt 0), the barrier, then ONE system-scope release before the
+    // status words (MI355X_MICROARCH.md, correctness boundaries): a release per thread wrote back the
+    // L2 sixteen times and cost more than the search
+    __builtin_amdgcn_s_waitcnt(0);
+    SYNC();
 }
 // The one-workgroup search from the staged queries on: frame staging, candidate lists, the fixed point
 // and the commit, shared by k_sbp_block (records) and k_sbp_kf_batch (points projected in registers).
@@ -1230,15 +1393,14 @@ __device__ __forceinline__ int blk_search(const FrameDev& fr, const BlkGeom& gm,
                                           float nnratio, int maxDist, int need_obs, const BlkIO& io, uint8_t* mt_sm,
                                           Reload&& reload, const int*& cnt_out) {
     const int n = fr.n;
-    const int nlev = fr.nlevels;
-    const int nbk = nlev * gm.NB * gm.NS;
-    float4* s_kp = (float4*)mt_sm;                 // {x, y, rank bits, uR} per bucket position
-    uint4* s_desc = (uint4*)(s_kp + n);            // 2 x uint4 per bucket position
-    int* s_ber = (int*)(s_desc + 2 * n);           // bucket bounds region (blk_be_words)
+    const BlkLds lds(n, fr.nlevels * gm.NB * gm.NS, BLK_ONE);
+    float4* s_kp = lds.kp(mt_sm);
+    uint4* s_desc = lds.desc(mt_sm);
+    int* s_ber = lds.ber(mt_sm);
     const int* s_be = s_ber + 3;                   // be[c] = start of bucket c, be[c + 1] = its end
-    int* s_first = s_ber + blk_be_words(nbk, MT_BLK_NT);   // two first[] states by keypoint index (then the commit's slots)
-    float* s_ang = (float*)(s_first + 2 * n);      // keypoint angles by index (the rotation check)
-    uint8_t* s_blk = (uint8_t*)(s_ang + n);        // blocked initially, by keypoint index
+    int* s_first = lds.first(mt_sm);
+    float* s_ang = lds.ang(mt_sm);
+    uint8_t* s_blk = lds.blk(mt_sm);
     __shared__ int s_flag, s_ws[MT_BLK_NT / 64], s_hist[MT_HISTO], s_cnt[2];
     __shared__ unsigned s_keep;
     const int tid = threadIdx.x;
@@ -1259,7 +1421,7 @@ __device__ __forceinline__ int blk_search(const FrameDev& fr, const BlkGeom& gm,
         res[i] = -1;
         obs[i] = QS[i].obs;
 #pragma unroll
-        for (int k = 0; k < MT_BLK_LIST; k++) L[i][k] = 0xFFFFFFFFu;
+        for (int k = 0; k < MT_BLK_LIST; k++) L[i][k] = BlkKey::kNoEntry;
         if (q >= nq) continue;
         const int c = blk_list<MODE>(QS[i], gm, s_kp, s_desc, s_be, s_blk, L[i]);
         npair += (unsigned)c;
@@ -1278,39 +1440,10 @@ __device__ __forceinline__ int blk_search(const FrameDev& fr, const BlkGeom& gm,
             const int q = tid + i * MT_BLK_NT;
             if (q >= nq) continue;   // (not break: the loop must unroll so the per-slot arrays stay in registers)
             // the first (and, MODE 0, second) list entries that no earlier query holds
-            // (the eight gate reads issued together, the selection in registers)
-            bool free_[MT_BLK_LIST];
-#pragma unroll
-            for (int k = 0; k < MT_BLK_LIST; k++)
-                free_[k] = L[i][k] != 0xFFFFFFFFu && fcur[L[i][k] & 0x1FFFu] >= q;
-            uint32_t e1 = 0xFFFFFFFFu, e2 = 0xFFFFFFFFu;
-            int found = 0;
-#pragma unroll
-            for (int k = 0; k < MT_BLK_LIST; k++) {
-                if (!free_[k] || found >= (MODE == 0 ? 2 : 1)) continue;
-                if (found == 0) e1 = L[i][k];
-                else e2 = L[i][k];
-                found++;
-            }
-            int result;
-            if (found < (MODE == 0 ? 2 : 1) && cnt[i] > MT_BLK_LIST) {
-                // the list ran out: the window again, with this pass's gates
-                const BlkQuery Q = reload(q);
-                unsigned long long k1 = ~0ull, k2 = ~0ull;
-                blk_enum<MODE>(Q, gm, s_kp, s_desc, s_be, s_blk, [&](unsigned long long key, int idx) {
-                    if (fcur[idx] < q) return;
-                    const bool lt1 = key < k1, lt2 = key < k2;   // selects, not a store through a chosen pointer
-                    k2 = lt1 ? k1 : (lt2 ? key : k2);
-                    k1 = lt1 ? key : k1;
-                });
-                result = blk_accept<MODE>(k1 != ~0ull ? (int)((k1 >> 4) & 0x1FFFu) : -1, (int)(k1 >> 40),
-                                          (int)(k1 & 15), k2 != ~0ull ? (int)(k2 >> 40) : 256,
-                                          k2 != ~0ull ? (int)(k2 & 15) : -1, nnratio, maxDist);
-            } else {
-                result = blk_accept<MODE>(e1 != 0xFFFFFFFFu ? (int)(e1 & 0x1FFFu) : -1, (int)(e1 >> 16),
-                                          (int)((e1 >> 13) & 7), e2 != 0xFFFFFFFFu ? (int)(e2 >> 16) : 256,
-                                          e2 != 0xFFFFFFFFu ? (int)((e2 >> 13) & 7) : -1, nnratio, maxDist);
-            }
+            const BlkPick pk = blk_pick<MODE == 0 ? 2 : 1>(
+                L[i], cnt[i], [&](int idx) { return fcur[idx] >= q; },
+                [&](auto&& f) { blk_enum<MODE>(reload(q), gm, s_kp, s_desc, s_be, s_blk, f); });
+            const int result = blk_accept<MODE>(pk.b1, pk.b2, nnratio, maxDist);
             if (result >= 0 && (!need_obs || obs[i] > 0)) atomicMin(&fnext[result], q);
             if (result != res[i]) {
                 res[i] = result;
@@ -1322,69 +1455,10 @@ __device__ __forceinline__ int blk_search(const FrameDev& fr, const BlkGeom& gm,
         // after pass t the first t queries are final, so at most nq + 1 passes change anything
         if (s_flag == 0 || pass > nq) break;
     }
-    // ---- the commit (k_mt_commit_count / _drop / _write in one block): the last writer of a slot
-    // wins, every assignment enters the rotation histogram, ComputeThreeMaxima's dropped bins clear
-    // their slots and count once per entry (ORBmatcher.cc:1775-1792,1864-1884) ----
-    int* s_res = s_first;   // the pass states are dead
-    for (int k = tid; k < n; k += MT_BLK_NT) s_res[k] = -1;
-    SYNC();
-    int nas = 0;
-    int bins[MT_BLK_QPT];
-#pragma unroll
-    for (int i = 0; i < MT_BLK_QPT; i++) {
-        const int q = tid + i * MT_BLK_NT;
-        bins[i] = -1;
-        if (q >= nq || res[i] < 0) continue;
-        atomicMax(&s_res[res[i]], q);
-        nas++;
-        if (io.checkOri) bins[i] = mt_rot_bin(qang[i], s_ang[res[i]]);
-    }
-    // per-wave counts, one LDS atomic per wave and distinct bin (the assignments of a frame fall in
-    // a few bins: same-address atomics from every lane serialise)
-    nas = wave_sum_dpp(nas);
-    if ((tid & 63) == 0 && nas) atomicAdd(&s_cnt[0], nas);
-    if (io.checkOri) {
-#pragma unroll
-        for (int i = 0; i < MT_BLK_QPT; i++) {
-            int b = bins[i];
-            for (unsigned long long act = __ballot(b >= 0); act; act = __ballot(b >= 0)) {
-                const int lead = __builtin_amdgcn_readlane(b, (int)__builtin_ctzll(act));
-                const unsigned long long same = __ballot(b == lead);
-                if ((tid & 63) == (int)__builtin_ctzll(same)) atomicAdd(&s_hist[lead], (int)__popcll(same));
-                if (b == lead) b = -1;
-            }
-        }
-    }
-    SYNC();
-    if (tid == 0) s_keep = io.checkOri ? mt_three_maxima_keep(s_hist) : 0xFFFFFFFFu;
-    SYNC();
-    int ndrop = 0;
-#pragma unroll
-    for (int i = 0; i < MT_BLK_QPT; i++) {
-        const int q = tid + i * MT_BLK_NT;
-        if (q >= nq || res[i] < 0 || bins[i] < 0 || ((s_keep >> bins[i]) & 1u)) continue;
-        s_res[res[i]] = -2;
-        io.mvp_out[res[i]] = -1;
-        ndrop++;
-    }
-    ndrop = wave_sum_dpp(ndrop);
-    if ((tid & 63) == 0 && ndrop) atomicAdd(&s_cnt[1], ndrop);
-    SYNC();
-    // the last writer of each slot that no dropped entry cleared stores its record's id
-#pragma unroll
-    for (int i = 0; i < MT_BLK_QPT; i++) {
-        const int q = tid + i * MT_BLK_NT;
-        if (q < nq && res[i] >= 0 && s_res[res[i]] == q) io.mvp_out[res[i]] = qid[i];
-    }
-    if (io.stats && npair) {
-        atomicAdd(&io.stats[0], npair);
-        atomicAdd(&io.stats[1], npair);
-    }
-    // every wave's slot writes complete (vmcnt 0), the barrier, then ONE system-scope release before the
-    // status words (MI355X_MICROARCH.md, correctness boundaries): a release per thread wrote back the
-    // L2 sixteen times and cost more than the search
-    __builtin_amdgcn_s_waitcnt(0);
-    SYNC();
+    // the pass states are dead: the commit's slots
+    blk_commit<MT_BLK_QPT, true>(
+        n, true, io, npair, BlkCommitLds{s_first, s_ang, s_hist, &s_keep, s_cnt}, [&](int i) { return res[i]; },
+        [&](int i) { return tid + i * MT_BLK_NT; }, [&](int i) { return qid[i]; }, [&](int i) { return qang[i]; });
     cnt_out = s_cnt;
     return pass + 1;
 }
@@ -1447,13 +1521,14 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_block2(FrameDev fr, BlkGeom g
     extern __shared__ __attribute__((aligned(16))) uint8_t mt_sm[];
     const int n = fr.n;
     const int nbk1 = fr.nlevels * gm.NB * gm.NS;   // buckets of one camera
-    float4* s_kp = (float4*)mt_sm;
-    uint4* s_desc = (uint4*)(s_kp + n);
-    int* s_ber = (int*)(s_desc + 2 * n);
+    const BlkLds lds(n, 2 * nbk1, BLK_TWO_LAST);
+    float4* s_kp = lds.kp(mt_sm);
+    uint4* s_desc = lds.desc(mt_sm);
+    int* s_ber = lds.ber(mt_sm);
     const int* s_be = s_ber + 3;
-    int* s_first = s_ber + blk_be_words(2 * nbk1, MT_BLK_NT);
-    float* s_ang = (float*)(s_first + 2 * n);
-    uint8_t* s_blk = (uint8_t*)(s_ang + n);
+    int* s_first = lds.first(mt_sm);
+    float* s_ang = lds.ang(mt_sm);
+    uint8_t* s_blk = lds.blk(mt_sm);
     __shared__ int s_flag, s_ws[MT_BLK_NT / 64], s_hist[MT_HISTO], s_cnt[2];
     __shared__ unsigned s_keep;
     const int tid = threadIdx.x;
@@ -1505,7 +1580,7 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_block2(FrameDev fr, BlkGeom g
         for (int sd = 0; sd < 2; sd++) {
             cnt[2 * i + sd] = 0;
 #pragma unroll
-            for (int k = 0; k < MT_BLK2_LIST; k++) L[2 * i + sd][k] = 0xFFFFFFFFu;
+            for (int k = 0; k < MT_BLK2_LIST; k++) L[2 * i + sd][k] = BlkKey::kNoEntry;
         }
         if (q >= nq) continue;
         int nwin = 0;
@@ -1536,36 +1611,18 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_block2(FrameDev fr, BlkGeom g
             const int q = tid + i * MT_BLK_NT;
             if (q >= nq) continue;
             const int e = 2 * q + sd;
-            // the first list entry no earlier entry holds (the gate reads issued together)
-            bool free_[MT_BLK2_LIST];
-#pragma unroll
-            for (int k = 0; k < MT_BLK2_LIST; k++)
-                free_[k] = L[j][k] != 0xFFFFFFFFu && fcur[L[j][k] & 0x1FFFu] >= e;
-            uint32_t e1 = 0xFFFFFFFFu;
-#pragma unroll
-            for (int k = MT_BLK2_LIST - 1; k >= 0; k--)
-                if (free_[k]) e1 = L[j][k];
-            int result;
-            if (e1 == 0xFFFFFFFFu && cnt[j] > MT_BLK2_LIST) {
-                // the list ran out: the window again, with this pass's gates (the smallest key = the
-                // first strict minimum in GetFeaturesInArea order)
+            // the first list entry no earlier entry holds (a rescan's smallest key = the first strict
+            // minimum in GetFeaturesInArea order)
+            const BlkPick pk = blk_pick<1>(L[j], cnt[j], [&](int idx) { return fcur[idx] >= e; }, [&](auto&& f) {
                 BlkQuery Q = blk_load<1>(fr, rq, q, th, a0, a1, 0.f);
                 if (sd) {
                     const float2 u = right_uv[q];
                     Q.x = u.x;
                     Q.y = u.y;
                 }
-                unsigned long long k1 = ~0ull;
-                blk_enum<3>(Q, gm, s_kp, s_desc, s_be, s_blk, [&](unsigned long long key, int idx) {
-                    if (fcur[idx] < e) return;
-                    k1 = key < k1 ? key : k1;
-                }, sd ? nbk1 : 0);
-                result = blk_accept<1>(k1 != ~0ull ? (int)((k1 >> 4) & 0x1FFFu) : -1, (int)(k1 >> 40), 0, 256, -1,
-                                       0.f, maxDist);
-            } else {
-                result = blk_accept<1>(e1 != 0xFFFFFFFFu ? (int)(e1 & 0x1FFFu) : -1, (int)(e1 >> 16), 0, 256, -1, 0.f,
-                                       maxDist);
-            }
+                blk_enum<3>(Q, gm, s_kp, s_desc, s_be, s_blk, f, sd ? nbk1 : 0);
+            });
+            const int result = blk_accept<1>(pk.b1, pk.b2, 0.f, maxDist);
             if (result >= 0 && obs[i] > 0) atomicMin(&fnext[result], e);
             if (result != res[j]) {
                 res[j] = result;
@@ -1577,62 +1634,11 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_block2(FrameDev fr, BlkGeom g
         if (s_flag == 0 || pass > 2 * nq) break;
     }
     BLK2_STAMP(4);
-    // ---- the commit: the last entry writing a slot wins, every assignment enters the rotation
-    // histogram, the dropped bins clear their slots and count once per entry ----
-    int* s_res = s_first;
-    for (int k = tid; k < n; k += MT_BLK_NT) s_res[k] = -1;
-    SYNC();
-    int nas = 0;
-    int bins[EPT];
-#pragma unroll
-    for (int j = 0; j < EPT; j++) {
-        const int i = j >> 1, q = tid + i * MT_BLK_NT;
-        bins[j] = -1;
-        if (q >= nq || res[j] < 0) continue;
-        atomicMax(&s_res[res[j]], 2 * q + (j & 1));
-        nas++;
-        if (io.checkOri) bins[j] = mt_rot_bin(qang[i], s_ang[res[j]]);
-    }
-    nas = wave_sum_dpp(nas);
-    if ((tid & 63) == 0 && nas) atomicAdd(&s_cnt[0], nas);
-    if (io.checkOri) {
-#pragma unroll
-        for (int j = 0; j < EPT; j++) {
-            int b = bins[j];
-            for (unsigned long long act = __ballot(b >= 0); act; act = __ballot(b >= 0)) {
-                const int lead = __builtin_amdgcn_readlane(b, (int)__builtin_ctzll(act));
-                const unsigned long long same = __ballot(b == lead);
-                if ((tid & 63) == (int)__builtin_ctzll(same)) atomicAdd(&s_hist[lead], (int)__popcll(same));
-                if (b == lead) b = -1;
-            }
-        }
-    }
-    SYNC();
-    if (tid == 0) s_keep = io.checkOri ? mt_three_maxima_keep(s_hist) : 0xFFFFFFFFu;
-    SYNC();
-    int ndrop = 0;
-#pragma unroll
-    for (int j = 0; j < EPT; j++) {
-        const int q = tid + (j >> 1) * MT_BLK_NT;
-        if (q >= nq || res[j] < 0 || bins[j] < 0 || ((s_keep >> bins[j]) & 1u)) continue;
-        s_res[res[j]] = -2;
-        io.mvp_out[res[j]] = -1;
-        ndrop++;
-    }
-    ndrop = wave_sum_dpp(ndrop);
-    if ((tid & 63) == 0 && ndrop) atomicAdd(&s_cnt[1], ndrop);
-    SYNC();
-#pragma unroll
-    for (int j = 0; j < EPT; j++) {
-        const int i = j >> 1, q = tid + i * MT_BLK_NT;
-        if (q < nq && res[j] >= 0 && s_res[res[j]] == 2 * q + (j & 1)) io.mvp_out[res[j]] = qid[i];
-    }
-    if (io.stats && npair) {
-        atomicAdd(&io.stats[0], npair);
-        atomicAdd(&io.stats[1], npair);
-    }
-    __builtin_amdgcn_s_waitcnt(0);
-    SYNC();
+    // the commit over both cameras' entries (entry 2 q + side); the pass states are dead: its slots
+    blk_commit<EPT, true>(
+        n, true, io, npair, BlkCommitLds{s_first, s_ang, s_hist, &s_keep, s_cnt}, [&](int j) { return res[j]; },
+        [&](int j) { return 2 * (tid + (j >> 1) * MT_BLK_NT) + (j & 1); }, [&](int j) { return qid[j >> 1]; },
+        [&](int j) { return qang[j >> 1]; });
     if (tid == 0) {
         if (io.stats) io.stats[2] = (unsigned long long)(pass + 1);
         mt_publish_status(io.st_host, io.seq, 0, s_cnt[0], s_cnt[1], pass + 1);
@@ -1659,9 +1665,7 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_block2(FrameDev fr, BlkGeom g
 // pass; more writers than that abort the search (status 2) and the caller runs the multi-launch form.
 // Each search keeps its MT_BLK_LIST smallest gate-independent keys; the last writer of each slot wins
 // (no rotation check in this search), nmatches counts every write (:130-137,196-204).
-#define MT_B4_WCAP 6
 #define MT_B4_LIST 4   // keys kept per search (registers: two searches per point, two points per thread)
-__host__ __device__ constexpr int blk4_bytes_per_kp() { return 16 + 32 + 4 + 2 * MT_B4_WCAP + 2 + 1; }
 __device__ __forceinline__ bool b4_taken(const uint16_t* wl, const int* wcnt, const uint8_t* blk0, int k, int e) {
     const int c = min(wcnt[k], MT_B4_WCAP);
     int last = -1;
@@ -1696,14 +1700,15 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_block4(FrameDev fr, BlkGeom g
     extern __shared__ __attribute__((aligned(16))) uint8_t mt_sm[];
     const int n = fr.n, nl = fr.nleft;
     const int nbk1 = fr.nlevels * gm.NB * gm.NS;
-    float4* s_kp = (float4*)mt_sm;
-    uint4* s_desc = (uint4*)(s_kp + n);
-    int* s_ber = (int*)(s_desc + 2 * n);
+    const BlkLds lds(n, 2 * nbk1, BLK_TWO_LOCAL);
+    float4* s_kp = lds.kp(mt_sm);
+    uint4* s_desc = lds.desc(mt_sm);
+    int* s_ber = lds.ber(mt_sm);
     const int* s_be = s_ber + 3;
-    int* s_wcnt = s_ber + blk_be_words(2 * nbk1, MT_BLK_NT);                  // writers per slot (this pass)
-    uint16_t* s_wl = (uint16_t*)(s_wcnt + n);                                  // their entries << 1 | Observations() > 0
-    int16_t* s_link = (int16_t*)(s_wl + (size_t)MT_B4_WCAP * n);              // l2r (left) / r2l (right) partner
-    uint8_t* s_blk = (uint8_t*)(s_link + n);                                   // held before the search
+    int* s_wcnt = lds.wcnt(mt_sm);         // writers per slot (this pass)
+    uint16_t* s_wl = lds.wl(mt_sm);        // their entries << 1 | Observations() > 0
+    int16_t* s_link = lds.link(mt_sm);     // l2r (left) / r2l (right) partner
+    uint8_t* s_blk = lds.blk(mt_sm);       // held before the search
     __shared__ int s_flag, s_ovf, s_ws[MT_BLK_NT / 64], s_cnt;
     const int tid = threadIdx.x;
     constexpr int QPT = MT_BLK_QPT;
@@ -1731,7 +1736,7 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_block4(FrameDev fr, BlkGeom g
         for (int sd = 0; sd < 2; sd++) {
             cnt[2 * i + sd] = 0;
 #pragma unroll
-            for (int k = 0; k < MT_B4_LIST; k++) L[2 * i + sd][k] = 0xFFFFFFFFu;
+            for (int k = 0; k < MT_B4_LIST; k++) L[2 * i + sd][k] = BlkKey::kNoEntry;
         }
         if (q >= nq) continue;
         const orbfe_map_point& mp = rq[q];
@@ -1782,43 +1787,19 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_block4(FrameDev fr, BlkGeom g
                 auto taken = [&](int k) {
                     return (sd && k == own) ? obs[i] > 0 : b4_taken(s_wl, s_wcnt, s_blk, k, e0);
                 };
-                bool free_[MT_B4_LIST];
-#pragma unroll
-                for (int k = 0; k < MT_B4_LIST; k++) free_[k] = L[j][k] != 0xFFFFFFFFu && !taken((int)(L[j][k] & 0x1FFFu));
-                uint32_t e1 = 0xFFFFFFFFu, e2 = 0xFFFFFFFFu;
-                int found = 0;
-#pragma unroll
-                for (int k = 0; k < MT_B4_LIST; k++) {
-                    if (!free_[k] || found >= 2) continue;
-                    if (found == 0) e1 = L[j][k];
-                    else e2 = L[j][k];
-                    found++;
-                }
-                int bi = -1, bd = 256, bl = -1, bd2 = 256, bl2 = -1;
-                if (found < 2 && cnt[j] > MT_B4_LIST) {
-                    // the list ran out: the window again, with this pass's gates
+                const BlkPick pk = blk_pick<2>(L[j], cnt[j], [&](int k) { return !taken(k); }, [&](auto&& f) {
                     const BlkQuery Q = sd ? b4_right(fr, rq[q], bFar, thFar) : blk_load<0>(fr, rq, q, th, bFar, 0, thFar);
-                    unsigned long long k1 = ~0ull, k2 = ~0ull;
-                    blk_enum<4>(Q, gm, s_kp, s_desc, s_be, s_blk, [&](unsigned long long key, int idx) {
-                        if (taken(idx)) return;
-                        const bool lt1 = key < k1, lt2 = key < k2;
-                        k2 = lt1 ? k1 : (lt2 ? key : k2);
-                        k1 = lt1 ? key : k1;
-                    }, sd ? nbk1 : 0);
-                    if (k1 != ~0ull) { bi = (int)((k1 >> 4) & 0x1FFFu); bd = (int)(k1 >> 40); bl = (int)(k1 & 15); }
-                    if (k2 != ~0ull) { bd2 = (int)(k2 >> 40); bl2 = (int)(k2 & 15); }
-                } else {
-                    if (e1 != 0xFFFFFFFFu) { bi = (int)(e1 & 0x1FFFu); bd = (int)(e1 >> 16); bl = (int)((e1 >> 13) & 7); }
-                    if (e2 != 0xFFFFFFFFu) { bd2 = (int)(e2 >> 16); bl2 = (int)((e2 >> 13) & 7); }
-                }
-                if (bi < 0 || bd > MT_TH_HIGH) continue;
-                if (bl == bl2 && bd > nnratio * bd2) {   // :124-125 / :190-191: `continue` to the next point
+                    blk_enum<4>(Q, gm, s_kp, s_desc, s_be, s_blk, f, sd ? nbk1 : 0);
+                });
+                const BlkCand &b1 = pk.b1, &b2 = pk.b2;
+                if (b1.idx < 0 || b1.dist > MT_TH_HIGH) continue;
+                if (b1.octave == b2.octave && b1.dist > nnratio * b2.dist) {   // :124-125 / :190-191: `continue` to the next point
                     go = false;
                     continue;
                 }
-                const int p = s_link[bi];
-                if (sd == 0) { r[0] = bi; r[1] = p; }
-                else { r[2] = p; r[3] = bi; }
+                const int p = s_link[b1.idx];
+                if (sd == 0) { r[0] = b1.idx; r[1] = p; }
+                else { r[2] = p; r[3] = b1.idx; }
             }
 #pragma unroll
             for (int b = 0; b < 4; b++) {
@@ -1832,40 +1813,12 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_block4(FrameDev fr, BlkGeom g
         if (s_flag == 0 || pass > nq) break;
     }
     const bool aborted = s_ovf != 0;
-    // ---- the commit: the last entry writing a slot wins; nmatches counts every write ----
-    int* s_res = s_wcnt;
-    for (int k = tid; k < n; k += MT_BLK_NT) s_res[k] = -1;
-    SYNC();
-    int nas = 0;
-    if (!aborted) {
-#pragma unroll
-        for (int i = 0; i < QPT; i++) {
-            const int q = tid + i * MT_BLK_NT;
-#pragma unroll
-            for (int b = 0; b < 4; b++) {
-                if (q >= nq || res[i][b] < 0) continue;
-                atomicMax(&s_res[res[i][b]], 4 * q + b);
-                nas++;
-            }
-        }
-    }
-    nas = wave_sum_dpp(nas);
-    if ((tid & 63) == 0 && nas) atomicAdd(&s_cnt, nas);
-    SYNC();
-    if (!aborted)
-#pragma unroll
-        for (int i = 0; i < QPT; i++) {
-            const int q = tid + i * MT_BLK_NT;
-#pragma unroll
-            for (int b = 0; b < 4; b++)
-                if (q < nq && res[i][b] >= 0 && s_res[res[i][b]] == 4 * q + b) io.mvp_out[res[i][b]] = rq[q].id;
-        }
-    if (io.stats && npair) {
-        atomicAdd(&io.stats[0], npair);
-        atomicAdd(&io.stats[1], npair);
-    }
-    __builtin_amdgcn_s_waitcnt(0);
-    SYNC();
+    // the commit (entry 4 q + b; no rotation check, nmatches counts every write); the writer counts are
+    // dead: its slots
+    blk_commit<4 * QPT, false>(
+        n, !aborted, io, npair, BlkCommitLds{s_wcnt, nullptr, nullptr, nullptr, &s_cnt},
+        [&](int j) { return res[j >> 2][j & 3]; }, [&](int j) { return 4 * (tid + (j >> 2) * MT_BLK_NT) + (j & 3); },
+        [&](int j) { return rq[tid + (j >> 2) * MT_BLK_NT].id; }, [](int) { return 0.f; });
     if (tid == 0) {
         if (io.stats) io.stats[2] = (unsigned long long)(pass + 1);
         mt_publish_status(io.st_host, io.seq, aborted ? 2 : 0, s_cnt, 0, pass + 1, io.ntm ? *io.ntm : 0);
@@ -1996,11 +1949,12 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_multi0(FrameDev fr, BlkGeom g
                                                           MultiIO io) {
     extern __shared__ __attribute__((aligned(16))) uint8_t mt_sm[];
     const int n = fr.n, nbk = fr.nlevels * gm.NB * gm.NS, tid = threadIdx.x;
-    float4* s_kp = (float4*)mt_sm;
-    uint4* s_desc = (uint4*)(s_kp + n);
-    int* s_ber = (int*)(s_desc + 2 * n);           // bucket bounds region (blk_be_words)
+    const BlkLds lds(n, nbk, BLK_MULTI0);
+    float4* s_kp = lds.kp(mt_sm);
+    uint4* s_desc = lds.desc(mt_sm);
+    int* s_ber = lds.ber(mt_sm);
     const int* s_be = s_ber + 3;
-    uint8_t* s_blk = (uint8_t*)(s_ber + blk_be_words(nbk, MT_BLK_NT));
+    uint8_t* s_blk = lds.blk(mt_sm);
     __shared__ int s_ws[MT_BLK_NT / 64];
     // the first round's records are read before the frame is staged: both memory round trips overlap
     BlkQuery Q0;
@@ -2041,9 +1995,7 @@ __global__ __launch_bounds__(MT_BLK_NT) void k_sbp_multi0(FrameDev fr, BlkGeom g
             lp[1] = make_uint4(L[4], L[5], L[6], L[7]);
             io.lcnt[q] = c | (Q.obs > 0 ? (int)0x80000000 : 0);
             // pass 0: no earlier query holds anything, the list's head decides
-            result = blk_accept<0>((int)(L[0] & 0x1FFFu), (int)(L[0] >> 16), (int)((L[0] >> 13) & 7),
-                                   L[1] != 0xFFFFFFFFu ? (int)(L[1] >> 16) : 256,
-                                   L[1] != 0xFFFFFFFFu ? (int)((L[1] >> 13) & 7) : -1, nnratio, 0);
+            result = blk_accept<0>(BlkKey::of_entry(L[0]), BlkKey::of_entry(L[1]), nnratio, 0);
             npair += (unsigned)c;
         }
         // the active list: wave offsets from an LDS counter, one global reservation per block
@@ -2086,37 +2038,11 @@ __global__ __launch_bounds__(MT_MULTI_NT) void k_sbp_multi(FrameDev fr, BlkGeom 
         const uint4* lp = (const uint4*)(io.lists + (size_t)q * MT_BLK_LIST);
         const uint4 l0 = lp[0], l1 = lp[1];
         const uint32_t L[MT_BLK_LIST] = {l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w};
-        bool free_[MT_BLK_LIST];
-#pragma unroll
-        for (int k = 0; k < MT_BLK_LIST; k++)
-            free_[k] = L[k] != 0xFFFFFFFFu && mt_fget(fcur[L[k] & 0x1FFFu], gen) >= q;
-        uint32_t e1 = 0xFFFFFFFFu, e2 = 0xFFFFFFFFu;
-        int found = 0;
-#pragma unroll
-        for (int k = 0; k < MT_BLK_LIST; k++) {
-            if (!free_[k] || found >= 2) continue;
-            if (found == 0) e1 = L[k];
-            else e2 = L[k];
-            found++;
-        }
-        int result;
-        if (found < 2 && c > MT_BLK_LIST) {
-            // the list ran out: the window again, over block 0's frame copy, with this pass's gates
-            const BlkQuery Q = blk_load<0>(fr, recs, q, th, bFar, 0, thFar);
-            unsigned long long k1 = ~0ull, k2 = ~0ull;
-            blk_enum<0>(Q, gm, io.g_kp, io.g_desc, io.g_be, io.g_blk, [&](unsigned long long key, int idx) {
-                if (mt_fget(fcur[idx], gen) < q) return;
-                const bool lt1 = key < k1, lt2 = key < k2;
-                k2 = lt1 ? k1 : (lt2 ? key : k2);
-                k1 = lt1 ? key : k1;
-            });
-            result = blk_accept<0>(k1 != ~0ull ? (int)((k1 >> 4) & 0x1FFFu) : -1, (int)(k1 >> 40), (int)(k1 & 15),
-                                   k2 != ~0ull ? (int)(k2 >> 40) : 256, k2 != ~0ull ? (int)(k2 & 15) : -1, nnratio, 0);
-        } else {
-            result = blk_accept<0>(e1 != 0xFFFFFFFFu ? (int)(e1 & 0x1FFFu) : -1, (int)(e1 >> 16), (int)((e1 >> 13) & 7),
-                                   e2 != 0xFFFFFFFFu ? (int)(e2 >> 16) : 256,
-                                   e2 != 0xFFFFFFFFu ? (int)((e2 >> 13) & 7) : -1, nnratio, 0);
-        }
+        // a list that ran out: the window again over block 0's frame copy in memory
+        const BlkPick pk = blk_pick<2>(L, c, [&](int idx) { return mt_fget(fcur[idx], gen) >= q; }, [&](auto&& f) {
+            blk_enum<0>(blk_load<0>(fr, recs, q, th, bFar, 0, thFar), gm, io.g_kp, io.g_desc, io.g_be, io.g_blk, f);
+        });
+        const int result = blk_accept<0>(pk.b1, pk.b2, nnratio, 0);
         if (result != prev) {
             io.assign[q] = result;
             ch = true;
@@ -4108,11 +4034,13 @@ inline int frustum_stage(const orbfe_frame* F, const FrustumIn& fin, const void*
 
 // k_sbp_block's bucket geometry for a frame: bands of 16 rows, then as many column strips (<= 32, >= 24
 // columns wide) as 8192 buckets and the LDS allow; false: the frame does not fit the block form
-// (ncam = 2: both cameras' bucket sets, k_sbp_block2 / k_sbp_block4; bpk: LDS bytes per keypoint)
-size_t blk_lds(int n, int nlev, const BlkGeom& gm, int ncam = 1, int bpk = 61) {
-    return (size_t)n * bpk + (size_t)blk_be_words(ncam * nlev * gm.NB * gm.NS, MT_BLK_NT) * 4 + 16;
+// (var: the kernel's BlkLds layout; the two-camera ones hold both cameras' bucket sets)
+size_t blk_lds(int n, int nlev, const BlkGeom& gm, BlkVar var = BLK_ONE) {
+    const int ncam = (var == BLK_TWO_LAST || var == BLK_TWO_LOCAL) ? 2 : 1;
+    return BlkLds(n, ncam * nlev * gm.NB * gm.NS, var).bytes();
 }
-bool blk_geom(const orbfe_frame* F, BlkGeom& gm, int ncam = 1, int bpk = 61) {
+bool blk_geom(const orbfe_frame* F, BlkGeom& gm, BlkVar var = BLK_ONE) {
+    const int ncam = (var == BLK_TWO_LAST || var == BLK_TWO_LOCAL) ? 2 : 1, bpk = BlkLds::bytes_per_kp(var);
     constexpr int BR = 16;
     if (!(F->max_y > 0.f && F->max_y < 65536.f && F->max_x > 0.f && F->max_x < 65536.f)) return false;
     gm.NB = (int)std::floor(F->max_y / BR) + 2;
@@ -4121,20 +4049,22 @@ bool blk_geom(const orbfe_frame* F, BlkGeom& gm, int ncam = 1, int bpk = 61) {
     const long budget = std::min<long>(8192, ((long)MT_LDS_MAX - (long)bpk * F->n - 4) / 4);
     gm.NS = (int)std::min<long>(std::min<long>(32, budget / std::max(lev_bands, 1)), (long)std::ceil(F->max_x / 24.f));
     if (gm.NS < 1) return false;
-    while (gm.NS > 1 && blk_lds(F->n, F->nlevels, gm, ncam, bpk) > MT_LDS_MAX) gm.NS--;   // the scan's padding
+    while (gm.NS > 1 && blk_lds(F->n, F->nlevels, gm, var) > MT_LDS_MAX) gm.NS--;   // the scan's padding
     gm.inv_sw = (float)gm.NS / (F->max_x + 1.f);
-    return blk_lds(F->n, F->nlevels, gm, ncam, bpk) <= MT_LDS_MAX;
+    return blk_lds(F->n, F->nlevels, gm, var) <= MT_LDS_MAX;
 }
 
-// sbp_run's one-launch form (k_sbp_block, k_sbp_block4): arguments already validated by sbp_run.
+// sbp_run's one-launch form (k_sbp_block, k_sbp_block2, k_sbp_block4): arguments already validated by
+// sbp_run. right_uv: a two-camera last-frame search's right-camera centres (lp: projected on the device).
 // kBlockAborted: k_sbp_block4 gave up (more writers of one slot than it tracks) before writing
 // anything; the caller runs the multi-launch form.
 constexpr int kBlockAborted = -1000;
 int sbp_block_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs, const void* queries, int nq,
                   const RecLayout& layout, float th, int a0, int a1, float thFar, float nnratio, int maxDist,
                   int checkOri, const BlkGeom& gm, const FrustumIn* fin, const DevIn* dev,
-                  const LastProjIn* lp = nullptr) {
+                  const LastProjIn* lp = nullptr, const float* right_uv = nullptr) {
     const int n = F->n;
+    const bool two2 = F->two_cams && mode == 1, two4 = F->two_cams && mode == 0;
     RecLayout rl = layout;
     Plan p;
     FramePlan fp;
@@ -4143,6 +4073,7 @@ int sbp_block_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* m
     const size_t o_q = dev ? 0 : fin ? p.upload(fin->pts, (size_t)nq * sizeof(orbfe_map_point_3d))
                                      : lp ? p.upload(lp->pts, (size_t)nq * sizeof(orbfe_last_point))
                                           : p.upload(queries, (size_t)nq * rl.stride);
+    const size_t o_ruv = !two2 ? 0 : lp ? p.scratch((size_t)nq * 8) : p.upload(right_uv, (size_t)nq * 8);
     const size_t o_rec = lp ? p.scratch((size_t)nq * sizeof(orbfe_proj_point)) : 0;   // device-projected records
     const size_t o_mvp = dev ? 0 : p.upload(mvp, (size_t)n * 4);
     const size_t o_obs = (dev || mode == 2) ? 0 : p.upload(mvp_obs, (size_t)n * 4);
@@ -4169,9 +4100,11 @@ int sbp_block_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* m
     int* ntm = fin ? ms_ptr<int>(o_ntm) : nullptr;
     // Tracking::SearchLocalPoints' isInFrustum, then the search (nothing in view: no match)
     if (fin) MSCHK(frustum_stage(F, *fin, q, nq, o_track, ntm, s, q, rl));
-    if (lp) {   // SearchByProjection(CurrentFrame, LastFrame)'s projection on the device
+    const float2* ruv = !two2 ? nullptr : lp ? ms_ptr<const float2>(o_ruv) : up_ptr<const float2>(o_ruv, zc);
+    if (lp) {   // SearchByProjection(CurrentFrame, LastFrame)'s projection on the device (two cameras: into both)
         hipLaunchKernelGGL(k_last_proj, dim3((nq + MT_NT - 1) / MT_NT), dim3(MT_NT), 0, s, *lp,
-                           up_ptr<const orbfe_last_point>(o_q, zc), nq, ms_ptr<orbfe_proj_point>(o_rec), (float2*)nullptr);
+                           up_ptr<const orbfe_last_point>(o_q, zc), nq, ms_ptr<orbfe_proj_point>(o_rec),
+                           two2 ? ms_ptr<float2>(o_ruv) : (float2*)nullptr);
         q = ms_ptr<const uint8_t>(o_rec);
     }
     const int32_t* mvp_in = dev ? mvp : up_ptr<const int32_t>(o_mvp, zc);
@@ -4181,10 +4114,12 @@ int sbp_block_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* m
     if (zc) memcpy(m.ho, mvp, (size_t)n * 4);   // the slots the search leaves alone keep their value
     const BlkIO io{mvp_in, obs_d, mvp_out, rl.stride, rl.id_off, rl.angle_off, checkOri, ntm, t_ms.hs_dev, seq,
                    stats.words, (zc && !fin && !lp) ? ms_ptr<uint4>(o_qdev) : nullptr};
-    const bool two4 = F->two_cams && mode == 0;
-    t_last_form = two4 ? ORBFE_SBP_FORM_BLOCK4 : ORBFE_SBP_FORM_BLOCK;
-    const size_t lds = two4 ? blk_lds(n, F->nlevels, gm, 2, blk4_bytes_per_kp()) : blk_lds(n, F->nlevels, gm);
-    if (two4)
+    t_last_form = two4 ? ORBFE_SBP_FORM_BLOCK4 : two2 ? ORBFE_SBP_FORM_BLOCK2 : ORBFE_SBP_FORM_BLOCK;
+    const size_t lds = blk_lds(n, F->nlevels, gm, two4 ? BLK_TWO_LOCAL : two2 ? BLK_TWO_LAST : BLK_ONE);
+    if (two2)
+        hipLaunchKernelGGL(k_sbp_block2, dim3(1), dim3(MT_BLK_NT), lds, s, fr, gm, (const orbfe_proj_point*)q, ruv, nq,
+                           th, a0, a1, maxDist, io);
+    else if (two4)
         hipLaunchKernelGGL(k_sbp_block4, dim3(1), dim3(MT_BLK_NT), lds, s, fr, gm, (const orbfe_map_point*)q, nq, th, a0,
                            thFar, nnratio, io);
     else if (mode == 0)
@@ -4208,59 +4143,6 @@ int sbp_block_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* m
     return st[1] - st[2];
 }
 
-// sbp_run's one-launch form for a two-camera frame's last-frame search (k_sbp_block2): host buffers
-// read in place from the mapped pinned staging, slots written to mapped pinned memory, the status
-// words awaited (as sbp_block_run); arguments already validated by sbp_run.
-int sbp_block2_run(const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs, const orbfe_proj_point* pts,
-                   const float* right_uv, int nq, float th, int a0, int a1, int maxDist, int checkOri,
-                   const BlkGeom& gm, const LastProjIn* lp = nullptr) {
-    const int n = F->n;
-    t_last_form = ORBFE_SBP_FORM_BLOCK2;
-    Plan p;
-    FramePlan fp;
-    fp.plan(p, F, true, false);
-    const size_t o_q = lp ? p.upload(lp->pts, (size_t)nq * sizeof(orbfe_last_point))
-                          : p.upload(pts, (size_t)nq * sizeof(orbfe_proj_point));
-    const size_t o_ruv = lp ? p.scratch((size_t)nq * 8) : p.upload(right_uv, (size_t)nq * 8);
-    const size_t o_rec = lp ? p.scratch((size_t)nq * sizeof(orbfe_proj_point)) : 0;
-    const size_t o_mvp = p.upload(mvp, (size_t)n * 4);
-    const size_t o_obs = p.upload(mvp_obs, (size_t)n * 4);
-    const size_t o_stats = stats_plan(p);
-    const size_t o_qdev = lp ? 0 : p.scratch((size_t)nq * sizeof(orbfe_proj_point));
-    MSCHK(ms_prepare(p, true));
-    MSCHK(ms_out_block((size_t)n, std::max<size_t>((size_t)n, 2048)));
-    MatchScratch& m = t_ms;
-    fp.zc = true;
-    hipStream_t s = t_ms.stream;
-    StatsScope stats;
-    MSCHK(stats.begin(o_stats, s));
-    MsTimer timer(s);
-    const FrameDev fr = fp.view();
-    const int seq = ++t_ms.seq;
-    memcpy(m.ho, mvp, (size_t)n * 4);   // the slots the search leaves alone keep their value
-    const BlkIO io{up_ptr<const int32_t>(o_mvp, true), up_ptr<const int32_t>(o_obs, true), m.ho_dev,
-                   kProjPointRec.stride, kProjPointRec.id_off, kProjPointRec.angle_off, checkOri, nullptr, t_ms.hs_dev,
-                   seq, stats.words, lp ? nullptr : ms_ptr<uint4>(o_qdev)};
-    const orbfe_proj_point* recs = up_ptr<const orbfe_proj_point>(o_q, true);
-    const float2* ruv = up_ptr<const float2>(o_ruv, true);
-    if (lp) {   // the projection into both cameras on the device; records and right centres in HBM
-        recs = ms_ptr<const orbfe_proj_point>(o_rec);
-        ruv = ms_ptr<const float2>(o_ruv);
-        hipLaunchKernelGGL(k_last_proj, dim3((nq + MT_NT - 1) / MT_NT), dim3(MT_NT), 0, s, *lp,
-                           up_ptr<const orbfe_last_point>(o_q, true), nq, ms_ptr<orbfe_proj_point>(o_rec),
-                           ms_ptr<float2>(o_ruv));
-    }
-    hipLaunchKernelGGL(k_sbp_block2, dim3(1), dim3(MT_BLK_NT), blk_lds(n, F->nlevels, gm, 2), s, fr, gm, recs, ruv, nq,
-                       th, a0, a1, maxDist, io);
-    HIPCHK(hipGetLastError());
-    timer.end();
-    MSCHK(ms_wait_seq(s, seq));
-    volatile int* st = t_ms.hs;
-    memcpy(mvp, m.ho, (size_t)n * 4);
-    MSCHK(stats.read(s));
-    return st[1] - st[2];
-}
-
 // the multi-block local-map search's persistent state (MatchScratch::mbuf): generation-tagged arrays
 // and self-resetting counters, zeroed once at allocation
 struct MultiBuf {
@@ -4273,9 +4155,6 @@ struct MultiBuf {
     static constexpr size_t counters = off_done, counters_bytes = off_nactive + 256 - off_done;
     static constexpr size_t bytes = off_nactive + 256;
 };
-size_t multi_lds(int n, int nlev, const BlkGeom& gm) {
-    return (size_t)n * 49 + (size_t)blk_be_words(nlev * gm.NB * gm.NS, MT_BLK_NT) * 4 + 16;
-}
 
 // sbp_run's multi-block form for single-camera local-map searches of more than MT_BLOCK_MAXQ points
 // (k_sbp_multi0 / k_sbp_multi): arguments already validated by sbp_run.
@@ -4358,7 +4237,7 @@ int sbp_multi_run(const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs, co
     // later passes walk the active queries (a fraction of nq): each thread's chain of dependent
     // loads (list -> gates) is the pass's latency, so more blocks (32: 10.8 us per pass, 128: 8.1)
     const int nb1 = std::min((nq + MT_MULTI_NT - 1) / MT_MULTI_NT, 256);
-    const size_t lds = multi_lds(n, F->nlevels, gm);
+    const size_t lds = blk_lds(n, F->nlevels, gm, BLK_MULTI0);
     // passes per round trip: as many as the previous search needed, plus one (a gated pass is one
     // short dispatch; another round trip costs far more)
     int batch = std::min(std::max(m.pass_hint[0] + 1, 2), 8);
@@ -4486,16 +4365,16 @@ int sbp_run(int mode, const orbfe_frame* F, int32_t* mvp, const int32_t* mvp_obs
     }
     // a two-camera frame's local-map search (SearchLocalPoints of a KannalaBrandt8 rig) in one
     // workgroup: four slot writes per point, the slots' writers tracked per pass (k_sbp_block4)
-    if (two && mode == 0 && n <= MT_BAND_MAXN && nq <= MT_BLOCK_MAXQ && blk_geom(F, gm, 2, blk4_bytes_per_kp())) {
+    if (two && mode == 0 && n <= MT_BAND_MAXN && nq <= MT_BLOCK_MAXQ && blk_geom(F, gm, BLK_TWO_LOCAL)) {
         const int r = sbp_block_run(0, F, mvp, mvp_obs, queries, nq, rl, th, a0, a1, thFar, nnratio, maxDist, 0, gm,
                                     fin, dev);
         if (r != kBlockAborted) return r;
     }
     // a two-camera frame's last-frame search (the per-frame Tracking call of a KannalaBrandt8 rig) in
     // one workgroup as well: both cameras' keypoints in LDS, two entries per point
-    if (two && mode == 1 && !dev && n <= MT_BAND_MAXN && nq <= MT_BLOCK_MAXQ && blk_geom(F, gm, 2))
-        return sbp_block2_run(F, mvp, mvp_obs, (const orbfe_proj_point*)queries, right_uv, nq, th, a0, a1, maxDist,
-                              checkOri, gm, lp);
+    if (two && mode == 1 && !dev && n <= MT_BAND_MAXN && nq <= MT_BLOCK_MAXQ && blk_geom(F, gm, BLK_TWO_LAST))
+        return sbp_block_run(1, F, mvp, mvp_obs, queries, nq, rl, th, a0, a1, thFar, nnratio, maxDist, checkOri, gm,
+                             nullptr, nullptr, lp, right_uv);
     // the multi-launch forms read host records: a device-projected search projects first and brings the
     // records back (searches beyond the one-workgroup limits only)
     std::vector<orbfe_proj_point> lp_rec;

@@ -424,6 +424,49 @@ def ladder(kind, th, obs):
     return s.case(f"ladder-obs{obs}", "blocked: a held slot with Observations() > 0 (keyframe: any held slot)", check)
 
 
+OVERFLOW = 18    # keys in the window: twice the longest kept candidate list (8) and two more
+TAKEN = 10
+
+
+def list_rank(F, qdesc, cands, best):
+    """1-based rank of `best` among a window's gate-independent candidates (the ones only the blocking state
+    decides: "blocked", "lost", "best") by (distance, enumeration order)."""
+    dist = lambda i: int(np.unpackbits(F.desc[i] ^ np.asarray(qdesc, np.uint8)).sum())   # noqa: E731
+    keys = sorted((dist(i), pos, i) for pos, (i, r) in enumerate(cands) if r in ("blocked", "lost", "best"))
+    return [i for _, _, i in keys].index(best) + 1
+
+
+def overflow_dist(j):
+    """Key j's distance to the probing query: strictly increasing, and the 11th (22) passes the local map's
+    ratio test against the 12th (40): 22 <= 0.8 * 40."""
+    return 2 + 2 * j if j <= TAKEN else 40 + 2 * (j - TAKEN - 1)
+
+
+def list_overflow(kind, th):
+    """One window of 18 keys at strictly increasing distances from the last query. Ten earlier queries (their
+    descriptors equal to one key each) take the ten nearest, so the last query's answer is its 11th key: beyond
+    any list of the 8 nearest gate-independent candidates, which a kernel that keeps such a list must notice."""
+    s = Scene(kind, th, check_ori=(kind != "local"))
+    b = base_desc(130)
+    u, v = f32(376.0), f32(240.0)
+    K = [s.kp(u + f32(0.125) * (j % 4), v + f32(0.125) * (j // 4), 0, flip(b, overflow_dist(j))) for j in range(OVERFLOW)]
+    E = [s.query(u, v, 0, flip(b, overflow_dist(j))) for j in range(TAKEN)]
+    P = s.query(u, v, 0, b)
+
+    def check(case, tr, mvp, n):
+        ids, t = case.q["id"], tr["q"][P]
+        for j in range(TAKEN):
+            assert tr["q"][E[j]]["best"] == K[j] and mvp[K[j]] == ids[E[j]]
+            assert rules_of(tr, P)[K[j]] == "blocked"
+        assert t["best"] == K[TAKEN] and t["bd"] == overflow_dist(TAKEN) and mvp[K[TAKEN]] == ids[P]
+        if kind == "local":
+            assert t["bd2"] == overflow_dist(TAKEN + 1)
+        assert list_rank(case.F, b, t["cands"], K[TAKEN]) == TAKEN + 1 > 8
+        assert sum(r in ("blocked", "lost", "best") for _, r in t["cands"]) == OVERFLOW
+        assert n == TAKEN + 1 and (mvp[K[TAKEN + 1:]] == -1).all()
+    return s.case("list-overflow", "blocked: the ten nearest keys held, the answer is the window's 11th", check)
+
+
 def preheld(kind, th):
     """A slot held before the search by a point without observations: free for the local map and the last
     frame, blocked for the keyframe form."""
@@ -631,7 +674,7 @@ def _build():
                 out.append(stereo_edge(kind, th))
             if kind == "lastframe":
                 out.append(stereo_fused(th))
-            out += [ladder(kind, th, 1), ladder(kind, th, 0), preheld(kind, th)]
+            out += [ladder(kind, th, 1), ladder(kind, th, 0), list_overflow(kind, th), preheld(kind, th)]
             if kind != "local":
                 for pname in PLANS:
                     out += [rotation(kind, 1, pname, True), rotation(kind, 1, pname, False)]

@@ -17,7 +17,8 @@ import numpy as np
 from oracle import sbp_definition as sd
 from orb_slam3_ros_amd.extractor import KEYPOINT_DTYPE
 from orb_slam3_ros_amd.matcher import MAP_POINT_DTYPE, MP_BAD, MP_IN_VIEW, MP_IN_VIEW_R, PROJ_POINT_DTYPE, MatchFrame
-from sbp_patterns import BOUNDS, MBF, NLEVELS, PAD_N, PLANS, SF, _plan_bins, base_desc, down, flip, up
+from sbp_patterns import (BOUNDS, MBF, NLEVELS, OVERFLOW, PAD_N, PLANS, SF, TAKEN, _plan_bins, base_desc, down, flip,
+                          list_rank, overflow_dist, up)
 
 f32 = np.float32
 QID = 5000
@@ -664,6 +665,32 @@ def lf_ladder(obs):
                   "no-sequence" if obs else "right-left-grid")
 
 
+def lf_list_overflow():
+    """The single-camera suite's list-overflow window on both cameras at once: 18 keys per camera at strictly
+    increasing distances from the last point, the ten nearest of each camera taken by ten earlier points, so the
+    last point's left and right answers are each window's 11th key."""
+    s = Scene2("lastframe2", TH_LF, check_ori=True)
+    b = base_desc(545)
+    u, v = site(17)
+    K = {sd_: [s.kp(sd_, u + f32(0.125) * (j % 4), v + f32(0.125) * (j // 4), 0, flip(b, overflow_dist(j)))
+               for j in range(OVERFLOW)] for sd_ in "LR"}
+    E = [s.pt(flip(b, overflow_dist(j)), (u, v), (u, v)) for j in range(TAKEN)]
+    P = s.pt(b, (u, v), (u, v))
+    exp = {K[sd_][j]: (E[j] if j < TAKEN else P) for sd_ in "LR" for j in range(TAKEN + 1)}
+
+    def check(c, tr):
+        for sd_ in "LR":
+            t = tr["q"][P][sd_]
+            for j in range(TAKEN):
+                assert tr["q"][E[j]][sd_]["best"] == c.g(K[sd_][j]) and rules_of(t)[c.g(K[sd_][j])] == "blocked"
+            assert (t["best"], t["bd"]) == (c.g(K[sd_][TAKEN]), overflow_dist(TAKEN))
+            assert list_rank(c.F, b, t["cands"], c.g(K[sd_][TAKEN])) == TAKEN + 1 > 8
+            assert sum(r in ("blocked", "lost", "best") for _, r in t["cands"]) == OVERFLOW
+        assert tr["bins"][0] == 2 * (TAKEN + 1)
+    return s.case("list-overflow", "blocked: the ten nearest keys of either camera held, the answers are the 11th",
+                  exp, 2 * (TAKEN + 1), check, "no-sequence")
+
+
 def lf_preheld():
     """Slots held before the search: 0 observations free, > 0 blocked, on both cameras."""
     s = Scene2("lastframe2", TH_LF)
@@ -872,7 +899,7 @@ def _build():
            own_partner_seen(), left_ratio_cancels(), left_far_right_runs(), gates(), right_radius(), right_window_edge(),
            right_ties_ratio(), list_depth(4), list_depth(5), ladder(False), ladder(True), cameras_apart()]
     out += [lf_two_entries(), lf_left_window(), lf_right_outside(), lf_right_claims(), lf_ladder(1), lf_ladder(0),
-            lf_preheld(), lf_no_uright_gate(), lf_gates()]
+            lf_list_overflow(), lf_preheld(), lf_no_uright_gate(), lf_gates()]
     for o in (0, NLEVELS - 1):
         out += [lf_level_range(o, False, False), lf_level_range(o, True, False), lf_level_range(o, False, True)]
     for p in LF_PLANS:

@@ -33,7 +33,7 @@ def test_case_inventory():
     for need in ("window-edge", "window-cells", "window-offset-bounds", "level-range-L0-std", "level-range-L7-fw",
                  "level-range-L0-fw", "level-range-L7-bw", "tie-levels", "tie-dup-zero", "distance-100", "distance-80",
                  "ratio-0.6", "ratio-0.7", "ratio-0.75", "ratio-0.8", "ratio-0.9", "stereo-edge", "stereo-fused",
-                 "ladder-obs1", "ladder-obs0", "preheld-obs0", "rot-half-way-ori1", "rot-tenth-60-ori1"):
+                 "ladder-obs1", "ladder-obs0", "list-overflow", "preheld-obs0", "rot-half-way-ori1", "rot-tenth-60-ori1"):
         assert need in names, need
     for kind, ths in (("local", {1, 3, 5}), ("lastframe", {1, 7}), ("kf", {1, 10})):
         assert {c.par["th"] for c in CASES if c.kind == kind} == ths

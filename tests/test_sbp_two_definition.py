@@ -32,8 +32,8 @@ def test_case_inventory():
                  "right-window-edge", "right-ties-ratio", "list-depth-4", "list-depth-5", "ladder", "ladder-reversed",
                  "cameras-apart"):
         assert need + "-local2" in names, need
-    for need in ("two-entries", "left-window", "right-outside", "right-claims", "ladder-obs1", "ladder-obs0", "preheld",
-                 "no-uright-gate", "gates", "level-range-L0-std", "level-range-L7-fw", "level-range-L0-fw",
+    for need in ("two-entries", "left-window", "right-outside", "right-claims", "ladder-obs1", "ladder-obs0", "list-overflow",
+                 "preheld", "no-uright-gate", "gates", "level-range-L0-std", "level-range-L7-fw", "level-range-L0-fw",
                  "level-range-L7-bw", "rot-ties-ori1", "rot-tenth-60-ori1", "rot-half-way-ori1", "rot-ties-ori0"):
         assert need + "-lastframe2" in names, need
     assert P.SEVEN_WRITERS in names
