@@ -1297,9 +1297,17 @@ int orbfe_matcher_last_sim3_passes(void);
  * 5 = how the last batch built `level`, int32[4] {one-launch pyramid tiles (0: the geometry does not
  *     fit it), builder (0 the caller's image, 1 one-launch pyramid, 2 row-streamed resize, 3 tiled
  *     resize), the level fits the row-streamed resize, pitch and every pointer 4-byte aligned}.
- * 6 = resize geometry of `level`, int32[6] {rz_rows, rz_cols, rs_rows as launched (0: not row-streamed), simd_end, xmax, pitch}.
+ * 6 = resize geometry of `level`, int32[6] {rz_rows, rz_cols, rs_rows as launched (0: not row-streamed), simd_end, xmax, pitch},
+ * 7 = the row-streamed resize's packed remainder strip of `level` as launched, int32[4] {lanes r, chunks
+ * per wave G, full items, packed items} (all 0 but the full items: not packed; all 0: not row-streamed).
  * Returns the element count. */
 int orbfe_debug_copy(orbfe_extractor* h, int what, int image, int level, void* dst, int cap_bytes);
+
+/* Debug/inspection (tests only): on != 0 makes the handle's later small batches (fewer than 16
+ * images) build the pyramid with the chained per-level launches at their small-batch shapes instead
+ * of the one-launch pyramid, so a test reaches those launches on any geometry; 0 restores the
+ * dispatch. Results are bit-identical either way. ORBFE_E_ARG for a NULL handle. */
+int orbfe_debug_chained_pyramid(orbfe_extractor* h, int on);
 
 /* Debug/inspection (tests only): fill, with the 32-bit `word`, every buffer of the handle that the
  * next call has to define for itself before it reads it, so that a test controls what a call finds

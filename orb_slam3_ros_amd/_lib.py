@@ -82,6 +82,7 @@ _SIGS = {
     "orbfe_descriptor_distance": (_c_int, [_vp, _vp]),
     "orbfe_debug_copy": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _c_int]),
     "orbfe_debug_fill_extractor": (_c_int, [_vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int64)]),
+    "orbfe_debug_chained_pyramid": (_c_int, [_vp, _c_int]),
     "orbfe_debug_fill_matcher": (_c_int, [ctypes.c_uint32, ctypes.POINTER(ctypes.c_int64)]),
     "orbfe_debug_block_sort": (_c_int, [_vp, _c_int]),
     "orbfe_version": (ctypes.c_char_p, []),

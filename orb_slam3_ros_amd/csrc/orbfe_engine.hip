@@ -150,6 +150,7 @@ struct orbfe_extractor {
     // how the last batch built its pyramid (orbfe_debug_copy what = 5): 1 k_pyramid, 2 k_resize_s, 3 k_resize
     int last_al0 = 0, last_builder[ORBFE_MAX_LEVELS] = {};
     int last_rs_rows[ORBFE_MAX_LEVELS] = {};   // k_resize_s rows per wave as launched (what = 6); 0: another builder
+    int last_rs_pack[ORBFE_MAX_LEVELS][4] = {};   // k_resize_s packed form as launched (what = 7): r, G, full items, packed items
     // extraction counter (every run_batch) and the matcher view of the last orbfe_frame_stereo call:
     // its id, left keypoint count, and the scale factors on the device (orbfe_frame_device_view)
     uint64_t frame_id = 0, fs_id = 0;
@@ -679,16 +680,31 @@ static int run_batch(orbfe_extractor* h, int B, const uint8_t* const* host_ptrs,
         h->last_al0 = al0 ? 1 : 0;
         for (int l = 1; l < g.nlevels; l++) h->last_builder[l] = fused_pyr ? 1 : (g.lv[l].rs_ok && (l > 1 || al0)) ? 2 : 3;
         for (int l = 1; l < g.nlevels; l++) h->last_rs_rows[l] = h->last_builder[l] == 2 ? gr.lv[l].rs_rows : 0;
+        memset(h->last_rs_pack, 0, sizeof h->last_rs_pack);
         if (fused_pyr)
             hipLaunchKernelGGL(k_pyramid, dim3(h->pt_n, B), dim3(PYR_NT), h->pt_lds, s, P, pitch, h->d_pyr, g.pyr_bytes, g,
                                h->d_ptile, h->pt_stride, h->pt_cap, al0 ? 1 : 0);
         for (int l = 1; l < g.nlevels && !fused_pyr; l++) {
             const OrbLevel& L = g.lv[l];
             if (L.rs_ok && (l > 1 || al0)) {
-                const int rows = gr.lv[l].rs_rows;
-                const int nstrips = (L.w + RS_COLS - 1) / RS_COLS, nitems = nstrips * ((L.h + rows - 1) / rows);
-                hipLaunchKernelGGL(k_resize_s, dim3((nitems + RS_WPB - 1) / RS_WPB, B), dim3(64 * RS_WPB), 0, s, P, pitch, h->d_pyr,
-                                   g.pyr_bytes, h->d_tab, gr, l, nstrips, nitems);
+                const int rows = gr.lv[l].rs_rows, nchunks = (L.h + rows - 1) / rows;
+                int nstrips = (L.w + RS_COLS - 1) / RS_COLS;
+                // a remainder strip of r <= 32 lanes goes to packed waves, G chunks each, numbered after
+                // the full items (orbfe_kernels.hip K1b). Large batches only: a small batch leaves the
+                // device mostly empty, so idle lanes cost it nothing and per-lane control would only
+                // lengthen each step of its latency-bound chain
+                const int r = small ? 0 : rs_pack_lanes(L.w), G = rs_pack_groups(r, rows);
+                int npacked = 0;
+                if (G >= 2) {
+                    nstrips--;
+                    npacked = (nchunks + G - 1) / G;
+                }
+                const int nfull = nstrips * nchunks, nitems = nfull + npacked;
+                const int pack[4] = {npacked ? r : 0, npacked ? G : 0, nfull, npacked};
+                memcpy(h->last_rs_pack[l], pack, sizeof pack);
+                const size_t lds = npacked ? (size_t)RS_WPB * rs_pack_entries(r, rows, L.h) * sizeof(uint2) : 0;
+                hipLaunchKernelGGL(k_resize_s, dim3((nitems + RS_WPB - 1) / RS_WPB, B), dim3(64 * RS_WPB), lds, s, P, pitch, h->d_pyr,
+                                   g.pyr_bytes, h->d_tab, gr, l, nstrips, nitems, nfull, npacked ? r : 0);
             } else {
                 const int tiles_y = (L.h + L.rz_rows - 1) / L.rz_rows;
                 dim3 grid((L.w + L.rz_cols - 1) / L.rz_cols, (tiles_y + RZ_TPB - 1) / RZ_TPB, B);
@@ -1460,6 +1476,11 @@ int orbfe_debug_copy(orbfe_extractor* h, int what, int image, int level, void* d
         memcpy(dst, geo, 24);
         return 6;
     }
+    else if (what == 7) {
+        if (cap_bytes < 16) return ORBFE_E_CAPACITY;
+        memcpy(dst, h->last_rs_pack[level], 16);
+        return 4;
+    }
     else if (what == 4) {
         if (!h->d_oct_ts) return 0;
         src = h->d_oct_ts + 64 * level; count = 64; bytes = 64 * 8;
@@ -1469,6 +1490,13 @@ int orbfe_debug_copy(orbfe_extractor* h, int what, int image, int level, void* d
     if ((size_t)cap_bytes < bytes) return ORBFE_E_CAPACITY;
     if (bytes) HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
     return count;
+}
+
+int orbfe_debug_chained_pyramid(orbfe_extractor* h, int on) {
+    if (!h) return ORBFE_E_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->no_fused_pyramid = on != 0;
+    return ORBFE_OK;
 }
 
 int orbfe_debug_fill_extractor(orbfe_extractor* h, uint32_t word, int64_t* bytes_out) {

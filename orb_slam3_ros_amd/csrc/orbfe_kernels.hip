@@ -383,16 +383,110 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k
 // window, columns 2, 3 from bytes 2..9; every output row reads rows (s - 1, s) for distinct s (the
 // table never clips). Bytes at or past the source width only ever meet a zero coefficient, so a
 // dword that would cross the row pitch is read from the row's last dword instead.
+//
+// Two forms of one item, chosen wave-uniformly per item in the level's one launch:
+//  - full (items [0, nfull), item = chunk * nstrips + strip): the wave owns one strip of one chunk.
+//    Everything about rows is wave-uniform and lives in SGPRs: the current output row, its table
+//    values (read by v_readlane from one table row per lane), the finish test, the row offset of
+//    each load (soffset) and the destination row.
+//  - packed (items nfull ...): a level whose width is no multiple of RS_COLS ends in a remainder
+//    strip of r = ceil((w mod RS_COLS) / 4) lanes. With r <= 32 the wave takes that strip of
+//    G = min(64 / r, RS_PK_ROWS / rs_rows) consecutive chunks instead of one: lane group j (lanes
+//    j r .. j r + r - 1) builds chunk item * G + j, with the same column setup in every group. The
+//    row state is then per lane: rows left in the chunk, (r1, b0, b1), the finish test, the load
+//    offset (voffset, clamped to the lane's own last source row) and the destination offset. The
+//    table rows of the wave's G chunks are consecutive: the wave copies them to its own LDS slice
+//    (dynamic, sized by the host per launch) once and each lane reads the entry after its current
+//    row one step ahead (an LDS read is counted apart from the row loads, so waiting for it leaves
+//    the RS_D - 1 row loads in flight; a table load from memory would drain them). The trip count is the largest source-row span of
+//    the wave's chunks; a lane past its chunk finishes nothing and stores to the slack, as do the
+//    groups past the level's last chunk and the lanes past G r. Per pixel the two forms compute
+//    the same expressions. r > 32 (G = 1) keeps the full form: scalar control is cheaper per step.
+// The column setup, the horizontal sums and the vertical pass are one source for both forms
+// (rs_columns, rs_hsums, rs_vertical): the full form's expressions, moved out of its body unchanged.
 // ---------------------------------------------------------------------------------------------
 #define RS_D 5               // rows of loads in flight per wave = RS_D - 1 (the loop body's unroll;
                              // with the dwordx3 loads: 2 / 3 / 5 / 7 -> 729 / 676 / 637 / 675 us per
                              // 1024 images, 7 costs a wave per SIMD)
 #define RS_ROWS 48           // output rows per wave (<= 64: one table row per lane; 16 / 32 / 48 / 64
-                             // with RS_D 5: 637 / 613 / 592 / 615 us per 1024 images)
+                             // with RS_D 5: 637 / 613 / 592 / 615 us per 1024 images; with the packed
+                             // remainder strips below 598 -> 546, profiles/r06_resize_packed_ab.txt)
 #define RS_COLS 256          // output columns per wave strip
 typedef unsigned short orbfe_ushort2_rs __attribute__((ext_vector_type(2)));
 #define RS_WPB 4   // waves per block (1 / 2 / 4 measured equal: r03_kernel_ab.txt item 24)
-// one wave's item of k_resize_s (image b, level l, item = chunk * nstrips + strip)
+#define RS_PK_ROWS 512       // most table rows a packed wave keeps in LDS (4 KB per wave, 16 KB per block: nine
+                             // blocks fit a CU, more waves than the registers allow, so never a limit)
+// the packed form's shape, for the launch arithmetic and the kernel alike: lanes of the level's
+// remainder strip (0: the width is a multiple of RS_COLS) and chunks per packed wave (< 2: not packed)
+__host__ __device__ inline int rs_pack_lanes(int w) { return ((w % RS_COLS) + 3) >> 2; }
+__host__ __device__ inline int rs_pack_groups(int r, int rows) {
+    const int a = r ? 64 / r : 0, b = RS_PK_ROWS / rows;
+    return a < b ? a : b;
+}
+// LDS table entries of one packed wave
+__host__ __device__ inline int rs_pack_entries(int r, int rows, int h) {
+    const int n = rs_pack_groups(r, rows) * rows;
+    return (n < h ? n : h) + 1;
+}
+// the 4 output columns at xq of a lane (both forms): v_perm selectors, packed coefficients,
+// stored-sum masks, the rounding rule per column; returns the window's first source byte
+struct RsCols {
+    uint32_t sel[4], coef[4], hmask[4];
+    bool vec[4];
+};
+__device__ __forceinline__ int rs_columns(const int16_t* tx, const OrbLevel& L, int xq, RsCols& C) {
+    const int base = tx[3 * min(xq, L.w - 1)] & ~3;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int x = min(xq + q, L.w - 1);
+        const bool lin = x < L.xmax;
+        const uint32_t a0 = lin ? (uint32_t)tx[3 * x + 1] : 2048u, a1 = lin ? (uint32_t)tx[3 * x + 2] : 0u;
+        const uint32_t off = (uint32_t)(tx[3 * x] - base) - (q >= 2 ? 2u : 0u);
+        C.sel[q] = 0x0c000c00u | (off & 7u) | (((off + 1u) & 7u) << 16);
+        C.coef[q] = (a0 << 4) | (a1 << 20);
+        C.vec[q] = x < L.simd_end;
+        C.hmask[q] = C.vec[q] ? 0xFFFF00u : 0xFFFFFFFFu;
+    }
+    return base;
+}
+// the stored horizontal sums of one source row's window (dwords w0..w2). LATE (the packed form, to
+// hold no masks in registers): the sums stay unmasked and rs_vertical masks them where it uses them
+template <bool LATE>
+__device__ __forceinline__ void rs_hsums(const RsCols& C, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t (&Hc)[4]) {
+    // bytes 2..9 of the window for columns 2, 3
+    const uint32_t c0 = __builtin_amdgcn_alignbyte(w1, w0, 2u), c1 = __builtin_amdgcn_alignbyte(w2, w1, 2u);
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const uint32_t pr = q < 2 ? __builtin_amdgcn_perm(w1, w0, C.sel[q]) : __builtin_amdgcn_perm(c1, c0, C.sel[q]);
+        Hc[q] = __builtin_amdgcn_udot2(__builtin_bit_cast(orbfe_ushort2_rs, pr),
+                                       __builtin_bit_cast(orbfe_ushort2_rs, C.coef[q]), 0u, false) &
+                (LATE ? 0xFFFFFFFFu : C.hmask[q]);
+    }
+}
+// the output dword of the row between stored sums Hp (first source row) and Hc (second); tail: the
+// lane holds scalar-tail columns (>= simd_end), whose sums are unmasked in either form
+template <bool LATE>
+__device__ __forceinline__ uint32_t rs_vertical(const RsCols& C, const uint32_t (&Hp)[4], const uint32_t (&Hc)[4],
+                                                uint32_t b0s, uint32_t b1s, bool tail) {
+    const uint32_t m = LATE ? 0xFFFF00u : 0xFFFFFFFFu;   // (a tail column's value here is replaced below)
+    uint32_t packed = 0;
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+        packed |= ((mulhi_u24(Hp[q] & m, b0s) + mulhi_u24(Hc[q] & m, b1s) + 2u) >> 2) << (8 * q);
+    if (tail) {
+        // (H0 b0 + H1 b1 + 2^21) >> 22 on the stored 16 H (unmasked for these columns):
+        // (16 H0 b0 + 16 H1 b1 + 2^25) >> 26 in 64 bits, the same floor
+        const uint64_t b0 = b0s >> 8, b1 = b1s >> 8;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const uint32_t vl = (uint32_t)(((uint64_t)Hp[q] * b0 + (uint64_t)Hc[q] * b1 + (1ull << 25)) >> 26);
+            const uint32_t m = C.vec[q] ? 0u : 0xFFu << (8 * q);
+            packed = (packed & ~m) | ((vl << (8 * q)) & m);
+        }
+    }
+    return packed;
+}
+// one wave's full item of k_resize_s (image b, level l, item = chunk * nstrips + strip)
 __device__ __forceinline__ void resize_s_item(const uint8_t* const* imgs, int in_pitch, uint8_t* pyr, int pyr_stride,
                                               const int16_t* __restrict__ tab, const OrbGeom& g, int l, int nstrips,
                                               int item, int b) {
@@ -407,22 +501,9 @@ __device__ __forceinline__ void resize_s_item(const uint8_t* const* imgs, int in
     const int16_t* ty = tab + L.tab_y;
     const int xq = strip * RS_COLS + 4 * lane;
     const bool act = xq < L.w;
-    // the lane's columns: v_perm selectors, packed coefficients, stored-sum masks
-    const int base = tx[3 * min(xq, L.w - 1)] & ~3;
-    uint32_t sel[4], coef[4], hmask[4];
-    bool vec[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int x = min(xq + q, L.w - 1);
-        const bool lin = x < L.xmax;
-        const uint32_t a0 = lin ? (uint32_t)tx[3 * x + 1] : 2048u, a1 = lin ? (uint32_t)tx[3 * x + 2] : 0u;
-        const uint32_t off = (uint32_t)(tx[3 * x] - base) - (q >= 2 ? 2u : 0u);
-        sel[q] = 0x0c000c00u | (off & 7u) | (((off + 1u) & 7u) << 16);
-        coef[q] = (a0 << 4) | (a1 << 20);
-        vec[q] = x < L.simd_end;
-        hmask[q] = vec[q] ? 0xFFFF00u : 0xFFFFFFFFu;
-    }
-    const bool lv_all = !act || (vec[0] && vec[1] && vec[2] && vec[3]);
+    RsCols C;
+    const int base = rs_columns(tx, L, xq, C);
+    const bool lv_all = !act || (C.vec[0] && C.vec[1] && C.vec[2] && C.vec[3]);
     // the chunk's vertical table rows, one per lane: (sy + 1, b0 << 8, b1 << 8) of row y0 + lane
     int t_s0 = 0, t_r1 = 0, t_b0 = 0, t_b1 = 0;
     if (y0 + lane < y1) {
@@ -443,34 +524,11 @@ __device__ __forceinline__ void resize_s_item(const uint8_t* const* imgs, int in
     // one source row s (window dwords w0..w2): its horizontal sums, then the output row whose
     // second source row is s, if any
     auto step = [&](int s, uint32_t w0, uint32_t w1, uint32_t w2) {
-        // bytes 2..9 of the window for columns 2, 3
-        const uint32_t c0 = __builtin_amdgcn_alignbyte(w1, w0, 2u), c1 = __builtin_amdgcn_alignbyte(w2, w1, 2u);
         uint32_t Hc[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const uint32_t pr = q < 2 ? __builtin_amdgcn_perm(w1, w0, sel[q]) : __builtin_amdgcn_perm(c1, c0, sel[q]);
-            Hc[q] = __builtin_amdgcn_udot2(__builtin_bit_cast(orbfe_ushort2_rs, pr),
-                                           __builtin_bit_cast(orbfe_ushort2_rs, coef[q]), 0u, false) &
-                    hmask[q];
-        }
+        rs_hsums<false>(C, w0, w1, w2, Hc);
         const bool fin = r1 == s;   // wave-uniform: a step that finishes no row skips the vertical pass
         uint32_t packed = 0;
-        if (fin) {
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-                packed |= ((mulhi_u24(Hp[q], b0s) + mulhi_u24(Hc[q], b1s) + 2u) >> 2) << (8 * q);
-            if (!lv_all) {   // the lane holding the level's scalar-tail columns (>= simd_end)
-                // (H0 b0 + H1 b1 + 2^21) >> 22 on the stored 16 H (unmasked for these columns):
-                // (16 H0 b0 + 16 H1 b1 + 2^25) >> 26 in 64 bits, the same floor
-                const uint64_t b0 = b0s >> 8, b1 = b1s >> 8;
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const uint32_t vl = (uint32_t)(((uint64_t)Hp[q] * b0 + (uint64_t)Hc[q] * b1 + (1ull << 25)) >> 26);
-                    const uint32_t m = vec[q] ? 0u : 0xFFu << (8 * q);
-                    packed = (packed & ~m) | ((vl << (8 * q)) & m);
-                }
-            }
-        }
+        if (fin) packed = rs_vertical<false>(C, Hp, Hc, b0s, b1s, !lv_all);   // !lv_all: the lane holding the level's scalar tail
         // a whole dword even for the level's last, partial group: the bytes past the width land
         // in the row's pitch padding, which nothing reads as pixels
         *(uint32_t*)(fin && act ? (uint32_t*)drow : slack) = packed;
@@ -530,15 +588,118 @@ __device__ __forceinline__ void resize_s_item(const uint8_t* const* imgs, int in
         }
     }
 }
+// one wave's packed item: the remainder strip (strip index nstrips, r lanes) of chunks item * G + j,
+// one per lane group j; s_tab: the wave's own rs_pack_entries() table entries
+__device__ __forceinline__ void resize_s_item_packed(const uint8_t* const* imgs, int in_pitch, uint8_t* pyr, int pyr_stride,
+                                                     const int16_t* __restrict__ tab, const OrbGeom& g, int l, int nstrips,
+                                                     int item, int b, int r, uint2* s_tab) {
+    const OrbLevel& L = g.lv[l];
+    const int lane = lane_id();
+    const int rows = L.rs_rows, G = rs_pack_groups(r, rows);
+    const int grp = small_div(lane, r), lg = lane - grp * r;
+    // the wave's table rows [R0, R0 + nrw) as (r1 - the chunk's first source row, b0 | b1 << 16), as
+    // a lane meets them when it finishes the row before: the first row of a chunk, and the entry
+    // past the last row, read -1 (the chunk before is finished: no further row)
+    const int16_t* ty = tab + L.tab_y;
+    const int R0 = item * G * rows, nrw = min(G * rows, L.h - R0);
+    for (int i = lane; i <= nrw; i += 64) {
+        const int16_t* tr = ty + 4 * (R0 + min(i, nrw - 1));
+        const int c0 = small_div(i, rows) * rows;   // the chunk's first row, relative to R0
+        const int rel = i == c0 || i == nrw ? -1 : tr[1] - ty[4 * (R0 + c0)];
+        s_tab[i] = make_uint2((uint32_t)rel, (uint32_t)(uint16_t)tr[2] | ((uint32_t)(uint16_t)tr[3] << 16));
+    }
+    WAVE_SYNC();
+    // this lane's chunk: its first table entry, its source rows [s_lo, s_hi]
+    const bool live = grp < G && R0 + grp * rows < L.h;   // not a group past G (lanes past G r) or past the level's last chunk
+    const int y0 = live ? R0 + grp * rows : R0, ylast = min(y0 + rows, L.h) - 1;
+    int ti = y0 - R0;   // table entry of the current row, then of the one after it
+    const uint2 e0 = s_tab[ti];
+    const int s_lo = ty[4 * y0], s_hi = ty[4 * ylast + 1];
+    int span = live ? s_hi - s_lo + 1 : 0;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) span = max(span, __shfl_xor(span, d, 64));
+    const int nsteps = __builtin_amdgcn_readfirstlane(span);
+    int spitch;
+    gptr_u8 src = level_base(imgs, in_pitch, pyr, pyr_stride, g, b, l - 1, &spitch);
+    uint8_t* img = pyr + (size_t)b * pyr_stride;
+    const int xq = nstrips * RS_COLS + 4 * lg;   // < L.w in every live lane (lg < r)
+    RsCols C;
+    const int base = rs_columns(tab + L.tab_x, L, xq, C);
+    const bool lv_all = !live || (C.vec[0] && C.vec[1] && C.vec[2] && C.vec[3]);
+    const bool tail = __builtin_amdgcn_ballot_w64(!lv_all) != 0;   // wave-uniform: some lane holds scalar-tail columns
+    // per-lane row state: the finishing source row of the current output row, relative to s_lo, and
+    // its coefficients; nxt: the entry of the row after it, read one finished row ahead
+    int r1 = live ? ty[4 * y0 + 1] - s_lo : -1;
+    uint32_t b0s = (e0.y & 0xFFFFu) << 8, b1s = (e0.y >> 16) << 8;
+    uint2 nxt = s_tab[++ti];
+    // byte offsets from the image's pyramid base: the destination dword, the lane's slack dword
+    uint32_t doff = (uint32_t)L.pyr_off + (uint32_t)y0 * (uint32_t)L.pitch + (uint32_t)xq;
+    const uint32_t soff = (uint32_t)g.pyr_slack + 4u * (uint32_t)lane;
+    uint32_t Hp[4] = {0u, 0u, 0u, 0u};
+    auto step = [&](int k, uint32_t w0, uint32_t w1, uint32_t w2) {   // source row s_lo + k of every lane
+        uint32_t Hc[4];
+        rs_hsums<true>(C, w0, w1, w2, Hc);
+        const bool fin = r1 == k;   // per lane: no branch, a lane that finishes no row stores to the slack
+        const uint32_t packed = rs_vertical<true>(C, Hp, Hc, b0s, b1s, tail);
+        *(uint32_t*)(img + (fin ? doff : soff)) = packed;
+        doff += fin ? (uint32_t)L.pitch : 0u;
+        r1 = fin ? (int)nxt.x : r1;   // -1 after the chunk's last row: the lane finishes nothing more
+        b0s = fin ? (nxt.y & 0xFFFFu) << 8 : b0s;
+        b1s = fin ? (nxt.y >> 16) << 8 : b1s;
+        ti = min(ti + (fin ? 1 : 0), nrw);
+        nxt = s_tab[ti];
+#pragma unroll
+        for (int q = 0; q < 4; q++) Hp[q] = Hc[q];
+    };
+    // the full form's loads and loop, with the row offset per lane in voffset: the lane's next row
+    // to load, clamped to its chunk's last source row
+    const uint64_t sp = (uint64_t)(uintptr_t)src;
+    const uint32_t sp_lo = __builtin_amdgcn_readfirstlane((uint32_t)sp), sp_hi = __builtin_amdgcn_readfirstlane((uint32_t)(sp >> 32));
+    const int sbytes = __builtin_amdgcn_readfirstlane(spitch * g.lv[l - 1].h);
+    const __amdgpu_buffer_rsrc_t srd =
+        __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)sp_hi << 32) | sp_lo), (short)0, sbytes, 0x00020000);
+    const int win = min(base, spitch - 4);
+    int lo = win + s_lo * spitch;
+    const int lo_hi = win + s_hi * spitch;
+    auto ld = [&](uint32_t (&w)[3]) {
+        typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
+        const u32x3 v = __builtin_bit_cast(u32x3, __builtin_amdgcn_raw_buffer_load_b96(srd, lo, 0, 0));
+        w[0] = v.x; w[1] = v.y; w[2] = v.z;
+        lo = min(lo + spitch, lo_hi);
+    };
+    uint32_t buf[RS_D][3];
+#pragma unroll
+    for (int d = 0; d < RS_D; d++) {
+        *(uint32_t*)(img + soff) = 0u;
+        ld(buf[d]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    for (int kb = 0; kb < nsteps; kb += RS_D) {
+#pragma unroll
+        for (int d = 0; d < RS_D; d++) {
+            step(kb + d, buf[d][0], buf[d][1], buf[d][2]);
+            ld(buf[d]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+}
+// items [0, nfull): full (nstrips strips per chunk); items [nfull, nitems): packed, the remainder
+// strip of pk_r lanes (strip index nstrips), when the host chose to pack it
 __global__ __launch_bounds__(64 * RS_WPB) void k_resize_s(const uint8_t* const* imgs, int in_pitch, uint8_t* pyr,
                                                   int pyr_stride, const int16_t* __restrict__ tab, OrbGeom g, int l,
-                                                  int nstrips, int nitems) {
+                                                  int nstrips, int nitems, int nfull, int pk_r) {
+    // dynamic LDS, none unless the launch has packed items: per wave the table rows of G chunks (at
+    // most the level's) and the entry past the last row. Sized by need: LDS held here is LDS that
+    // the k_fast blocks running beside the chain cannot have
+    extern __shared__ uint2 s_tab[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lb = xcd_logical(block_linear(), gridDim.x * gridDim.y);
     const int bx = lb % gridDim.x, b = lb / gridDim.x;
     const int item = bx * RS_WPB + wave;
     if (item >= nitems) return;
-    resize_s_item(imgs, in_pitch, pyr, pyr_stride, tab, g, l, nstrips, item, b);
+    if (item < nfull) resize_s_item(imgs, in_pitch, pyr, pyr_stride, tab, g, l, nstrips, item, b);
+    else resize_s_item_packed(imgs, in_pitch, pyr, pyr_stride, tab, g, l, nstrips, item - nfull, b, pk_r,
+                              s_tab + wave * rs_pack_entries(pk_r, g.lv[l].rs_rows, g.lv[l].h));
 }
 
 // ---------------------------------------------------------------------------------------------
